@@ -8,9 +8,12 @@ screen -> seed-index lookup -> chaining -> ANI/AF) and bring the hit list back t
 The ONE JSON line (rank 0) is the CONTRACT JOB - the job `north_star`'s target is quoted on, BASELINE.json configs[2] on the GPUs given: all-vs-all of 10 000
 synthetic ~5 Mb genomes (100 families of 100), 10^8 pairs, ~10^6 of them chained, c=125 marker_c=1000 k=15; a FIXED job (`scaling: "strong"`): at N>1 the references are
 sharded over the ranks, the shards' sketches all-gathered as the query side and the 20-byte hit records all-gathered once, so `--gpus N` reports the same job as N=1.
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it builds the genomes, warms up, times EXACTLY K steps, writes
+`--dump-outputs DIR` if given (the last timed step's hit records and per-query offsets as DIR/<name>.npy) and prints the line (`ms_per_step` = one timed step).
+Everything else is measured only with `--full`:
 `host_to_host` beside `value` is the same job from ASCII in HOST memory; `extras.oracle_check` = 8 random hits of the step recomputed by the CPU oracle;
 `extras.scaling_model` = a SINGLE-GPU EMULATION of rank 0's share of the 2-, 4- and 8-way job (no multi-GPU node was available: a prediction, not a measurement).
-At N=1 the default run then also measures the other configurations `north_star` names, each as an entry of `extras.workloads` with its own ms/step, hits,
+At N=1 the --full run then also measures the other configurations `north_star` names, each as an entry of `extras.workloads` with its own ms/step, hits,
 dominant-kernel `roofline` and a bounded `cpu_baseline`:
   search_1k         BASELINE configs[1]: 1 query vs 1 000 synthetic ~5 Mb refs (the headline of rounds 1-5), with its host-memory API legs
   allvsall_1k_*     SURVEY.md 8(d)'s harder generator variants (genomes cut into contigs / with block rearrangements), 8 hits of each recomputed by the oracle
@@ -20,7 +23,7 @@ dominant-kernel `roofline` and a bounded `cpu_baseline`:
                     pairs are checked against the CPU oracle outside the timed region
 (`--no-workloads` skips them; `--workload X` runs X alone as the line; `--refs N` without `--workload` runs the contract job at N genomes.)
 
-Every line / entry carries
+Every line / entry of a --full run carries
   roofline      the workload's dominant kernel among those with a stated algorithmic byte count, timed with HIP events
                 on the library's stream: achieved = algorithmic bytes / kernel time, against the 8 TB/s HBM peak; `traffic` = HBM bytes
                 from an offline rocprofv3 --pmc pass scaled by the run's units when profiles/ holds one for that kernel, else null
@@ -152,7 +155,7 @@ def compact_line(full, full_path=None):
         line["clock_mhz"] = _sig(full["clock"].get("shader_clock_mhz"))
     if "copy_bw" in full:
         line["copy_bw_GBps"] = _sig(full["copy_bw"].get("GBps"))
-    if "kernel_ms_per_step" in full:
+    if full.get("kernel_ms_per_step"):
         line["kernel_ms_per_step"] = {k: _sig(v, 4) for k, v in full["kernel_ms_per_step"].items()}
     ex_full = full.get("extras", {})
     ex = {}
@@ -855,9 +858,11 @@ def records_digest(recs):
     return h.hexdigest()[:16]
 
 
-def run_allvsall(job, steps, warmup, n_total, cpu_queries, variant="plain", verify_hits=0, host_leg=False, model_ranks=()):
+def run_allvsall(job, steps, warmup, n_total, cpu_queries, variant="plain", verify_hits=0, host_leg=False, model_ranks=(), kernel_table=True, outputs=None):
     """BASELINE configs[2] shape: every genome against a database of all of them (families of 100). N=1: one psk_query_many. N>1: the
-    FIXED job of n_total genomes is sharded over the ranks (strong scaling) and run through parallel.ShardedDatabase.all_vs_all_records."""
+    FIXED job of n_total genomes is sharded over the ranks (strong scaling) and run through parallel.ShardedDatabase.all_vs_all_records.
+    kernel_table=False: no per-kernel table (it takes one more step of its own) and no roofline. `outputs` (a dict, N=1): receives the
+    last timed step's hit records and per-query offsets."""
     torch, rank, world, args = job.torch, job.rank, job.world, job.args
     n_families = max(1, n_total // 100)
     anc_lens, fam_of = family_layout(3, n_total, n_families)
@@ -893,11 +898,13 @@ def run_allvsall(job, steps, warmup, n_total, cpu_queries, variant="plain", veri
         dt, n_hits, kern, work, clock = timed_loop(eng, step, steps, warmup, lambda: job.fence(eng))
         step_ms = list(getattr(timed_loop, "last_step_ms", []))      # every timed step's own wall time (the line's ms_per_step is their mean)
         recs = last["recs"]      # psk_hit_min: `query` = the hit's query within the call
+        if outputs is not None:
+            outputs["recs"], outputs["offs"] = recs, last["offs"]
         digest = records_digest(recs)
         # The timed steps keep two batches in flight on two lanes (query_many.hip: rounds of >= 2^31 (pair, seed) items): their kernels share the chip and a bracket's
         # duration says little about the kernel. The per-kernel table comes from ONE more step run as a single chain of launches (PSK_PIPELINE=0), outside the timed region.
         table_step = None
-        if "PSK_PIPELINE" not in os.environ:
+        if kernel_table and "PSK_PIPELINE" not in os.environ:
             os.environ["PSK_PIPELINE"] = "0"
             try:
                 dt1, _, kern, work, _ = timed_loop(eng, step, 1, 0, lambda: job.fence(eng))
@@ -906,7 +913,7 @@ def run_allvsall(job, steps, warmup, n_total, cpu_queries, variant="plain", veri
                 table_step = {"mode": "one chain of launches (PSK_PIPELINE=0), one step outside the timed region", "ms_per_step": dt1 * 1e3}
             finally:
                 del os.environ["PSK_PIPELINE"]
-        table = kernel_rooflines(kern, 1 if table_step else steps, {"bases": bases_local, "c": 125, "marker_c": 1000, **work}, job.pmc.get("allvsall10k" if (n_total >= 10000 and "allvsall10k" in job.pmc) else "allvsall", {}))      # (the 10 000 x 10 000 job has a counter pass of its own)
+        table = kernel_rooflines(kern, 1 if table_step else steps, {"bases": bases_local, "c": 125, "marker_c": 1000, **work}, job.pmc.get("allvsall10k" if (n_total >= 10000 and "allvsall10k" in job.pmc) else "allvsall", {})) if kernel_table else {}      # (the 10 000 x 10 000 job has a counter pass of its own)
         shape = {"plain": "single-contig genomes, substitutions only", "contigs": "every genome cut into 1-80 contigs",
                  "sv": "20 block inversions / translocations of 5-50 kb per genome on top of the substitutions"}[variant]
         line = {"ms_per_step": dt / steps * 1e3, "steps": steps, "warmup": warmup, "value": float(n_total) * n_total * steps / dt, "unit": "genome-pairs/s",
@@ -1342,6 +1349,33 @@ def mammalian_verify_host(contigs, recs, qoffs, n_genomes, verify_pairs, n_hits)
     return check, cpu
 
 
+DUMP_BUDGET = 64_000_000      # bytes --dump-outputs may write (the .npy headers included)
+
+
+def dump_outputs(out_dir, recs, offs, budget=DUMP_BUDGET):
+    """--dump-outputs: what the timed path handed its caller in its last step, one array per field - the hit records (psk_hit_min, in the
+    order the library returned them: hit_query, hit_learned, hit_ref_index, hit_ani, hit_af_query, hit_af_ref) and the per-query offsets
+    into them (query_offsets). Integers as float64 (exact), floats as float32. Above `budget` bytes a fixed, seeded sample of the hits is
+    written instead, sorted, with the sampled positions as hit_index."""
+    q = recs["query"].astype(np.uint32)
+    cols = {"hit_query": (q & np.uint32(0x7FFFFFFF)).astype(np.float64), "hit_learned": (q >> np.uint32(31)).astype(np.float32),
+            "hit_ref_index": recs["ref_index"].astype(np.float64), "hit_ani": recs["ani"].astype(np.float32),
+            "hit_af_query": recs["af_query"].astype(np.float32), "hit_af_ref": recs["af_ref"].astype(np.float32)}
+    arrays = {"query_offsets": np.asarray(offs).astype(np.float64)}
+    per_hit = sum(a.itemsize for a in cols.values())
+    n = len(recs)
+    if n * per_hit + arrays["query_offsets"].nbytes > budget:
+        keep = (budget - arrays["query_offsets"].nbytes - 4096) // (per_hit + 8)      # (4096: the headers of the eight files)
+        idx = np.sort(np.random.default_rng(20240).choice(n, size=keep, replace=False))
+        cols = {k: a[idx] for k, a in cols.items()}
+        cols["hit_index"] = idx.astype(np.float64)
+    arrays.update(cols)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: a.shape for k, a in arrays.items()}
+
+
 # ------------------------------------------------------------------ main
 def main():
     ap = argparse.ArgumentParser()
@@ -1352,7 +1386,7 @@ def main():
     ap.add_argument("--workload", choices=["search", "allvsall", "metagenome", "mammalian"], default=None,
                     help="default (no flag) = the contract job: all-vs-all of 10 000 genomes (BASELINE configs[2], the job north_star's target is quoted on; a FIXED job, sharded over the ranks at N>1: strong scaling), "
                          "with the other configurations under extras.workloads at N=1; a named workload runs alone as the line (search = BASELINE configs[1]: 1 query vs 1 000 refs per GPU, weak scaling)")
-    ap.add_argument("--no-workloads", action="store_true", help="the default run at N=1: skip extras.workloads (search 1 x 1 000, all-vs-all 1k variants, metagenome 100k, mammalian 8 x 3 Gb)")
+    ap.add_argument("--no-workloads", action="store_true", help="the --full run at N=1: skip extras.workloads (search 1 x 1 000, all-vs-all 1k variants, metagenome 100k, mammalian 8 x 3 Gb)")
     ap.add_argument("--queries", type=int, default=10000, help="metagenome: number of query contigs")
     ap.add_argument("--contig-mb", type=int, default=125, help="mammalian: contig length in Mb (24 contigs per genome; 125 = 3 Gb genomes)")
     ap.add_argument("--api-queries", type=int, default=10000, help="metagenome: contigs also sent one by one through Database.query() from host bytes (0 = skip)")
@@ -1362,12 +1396,21 @@ def main():
     ap.add_argument("--comm", choices=["torch", "capi"], default="torch", help="N>1: who moves the exchange steps — torch.distributed, or the library's own RCCL communicator (psk_comm_*)")
     ap.add_argument("--exchange-batch", type=int, default=1024, help="allvsall N>1: genomes per rank and round of the sketch all-gather (1 024: a round of 5 Mb genomes is then large enough - 2^31 (pair, seed) items - for two batches in flight; the single-GPU emulation of a rank: 7.35 x at N = 8 against 6.79 x with 256)")
     ap.add_argument("--share-gpu", action="store_true", help="dry-run aid: every rank uses device 0 (needs --backend gloo); never for reported numbers")
-    ap.add_argument("--cpu-sample", type=int, default=1000, help="CPU-baseline sample size (0 = skip): search: references (1000 = the whole workload, ~10-20 s); allvsall: queries (capped at 128); metagenome: contigs (capped at 512)")
+    ap.add_argument("--cpu-sample", type=int, default=1000, help="CPU-baseline sample size of a --full run (0 = skip): search: references (1000 = the whole workload, ~10-20 s); allvsall: queries (capped at 128); metagenome: contigs (capped at 512)")
     ap.add_argument("--variant", choices=["plain", "contigs", "sv"], default="plain", help="allvsall at N=1: the generator variant of SURVEY.md 8(d) - genomes cut into 1-80 contigs / 20 block rearrangements per genome")
-    ap.add_argument("--no-api", action="store_true", help="skip the host-memory API extras (N=1 search only)")
-    ap.add_argument("--no-host-leg", action="store_true", help="the default run at N=1: skip the job from ASCII in HOST memory (host_to_host; needs ~55 GB of host memory)")
-    ap.add_argument("--emulate-rank-of", type=int, nargs="*", default=None, help="N=1 all-vs-all: after the timed steps, time rank 0's share of the N-way job on this one GPU for every N given (default run: 2 4 8) -> extras.scaling_model; an emulation, not a measurement")
+    ap.add_argument("--no-api", action="store_true", help="skip the host-memory API extras of a --full run (N=1 search only)")
+    ap.add_argument("--no-host-leg", action="store_true", help="the --full run at N=1: skip the job from ASCII in HOST memory (host_to_host; needs ~55 GB of host memory)")
+    ap.add_argument("--emulate-rank-of", type=int, nargs="*", default=None, help="N=1 all-vs-all: after the timed steps, time rank 0's share of the N-way job on this one GPU for every N given (--full run: 2 4 8) -> extras.scaling_model; an emulation, not a measurement")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: copy bandwidth, CPU baselines, oracle checks, the host-memory leg, the scaling emulation, "
+                                                        "the per-kernel table step and rooflines, extras.workloads, the full object on disk. Without it a run sets up, warms up, "
+                                                        "times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="all-vs-all on one GPU: after the timed steps, write what the last timed step returned "
+                                                                        "(hit records and per-query offsets) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.workload not in (None, "allvsall") or args.gpus != 1):
+        ap.error("--dump-outputs writes the all-vs-all job's hits on one GPU (--gpus 1, no --workload or --workload allvsall)")
 
     # --gpus N without a launcher: this process starts the N ranks itself, BEFORE torch is imported or any HIP call is made
     if spawn_decision(args.gpus, os.environ):
@@ -1396,8 +1439,8 @@ def main():
         else:
             dist.init_process_group(backend=args.backend, rank=rank, world_size=world)
     job = Job(torch, device, local_rank, rank, world, dist, coll_device, args)
-    job.copy_bw = device_copy_bandwidth(torch, device)
-    cpu_n = args.cpu_sample if world == 1 else 0
+    job.copy_bw = device_copy_bandwidth(torch, device) if args.full else None
+    cpu_n = args.cpu_sample if (world == 1 and args.full) else 0
 
     def as_line(entry, workload, extra_cfg=None):
         """a non-headline workload run alone: its entry re-shaped into the contract's line"""
@@ -1416,13 +1459,17 @@ def main():
     if contract:
         args.workload = "allvsall"
     if args.workload == "search":
-        line = run_search(job, args.steps, args.warmup, args.refs or N_REFS, cpu_n, with_api=(world == 1 and not args.no_api))
+        line = run_search(job, args.steps, args.warmup, args.refs or N_REFS, cpu_n, with_api=(world == 1 and args.full and not args.no_api))
     elif args.workload == "allvsall":
         n_total = args.refs or (10000 if contract else 1000)
         full_job = contract and args.variant == "plain"
-        model_ranks = args.emulate_rank_of if args.emulate_rank_of is not None else ([2, 4, 8] if (full_job and not args.no_workloads) else [])
+        model_ranks = args.emulate_rank_of if args.emulate_rank_of is not None else ([2, 4, 8] if (full_job and args.full and not args.no_workloads) else [])
+        outputs = {} if args.dump_outputs else None
         e = run_allvsall(job, args.steps, args.warmup, n_total, min(cpu_n, 128), variant=args.variant, verify_hits=8 if (cpu_n > 0 and world == 1) else 0,
-                         host_leg=(full_job and world == 1 and not args.no_host_leg), model_ranks=model_ranks if world == 1 else ())
+                         host_leg=(full_job and world == 1 and args.full and not args.no_host_leg), model_ranks=model_ranks if world == 1 else (),
+                         kernel_table=args.full, outputs=outputs)
+        if outputs is not None and rank == 0:
+            dump_outputs(args.dump_outputs, outputs["recs"], outputs["offs"])
         if e:
             line = as_line(e, "allvsall", {"genomes": n_total, "parallelism": f"references sharded over {world} GPU(s)" + (f"; the shards' sketches all-gathered as the query side, hit records all-gathered once ({args.comm})" if world > 1 else "")})
             line["scaling"] = "strong"
@@ -1430,7 +1477,7 @@ def main():
                 line["host_to_host"] = e["host_to_host"]
             if e.get("exchange"):
                 line["extras"]["exchange"] = e["exchange"]
-        if full_job and world == 1 and not args.no_workloads:
+        if full_job and world == 1 and args.full and not args.no_workloads:
             t0 = time.perf_counter()
             wl = {}
             sl = run_search(job, 10, 2, N_REFS, cpu_n, with_api=not args.no_api)      # BASELINE configs[1]: the former headline
@@ -1445,7 +1492,7 @@ def main():
             line["extras"]["workloads"] = wl
             line["extras"]["workloads_wall_s"] = time.perf_counter() - t0
     elif args.workload == "metagenome":
-        m = run_metagenome(job, args.steps, args.warmup, args.refs or 5000, args.queries, (args.faster_small,), min(cpu_n, 512), args.api_queries)
+        m = run_metagenome(job, args.steps, args.warmup, args.refs or 5000, args.queries, (args.faster_small,), min(cpu_n, 512), args.api_queries if args.full else 0)
         if rank == 0:
             e = m["faster_small" if args.faster_small else "rescue"]
             line = as_line(e, "metagenome")
@@ -1458,15 +1505,16 @@ def main():
         line = as_line(e, "mammalian") if rank == 0 else None
     if rank == 0 and line is not None:
         line["n_gpus"] = world
-        line["copy_bw"] = job.copy_bw
-        for r in [line.get("roofline")] + [w.get("roofline") for w in line.get("extras", {}).get("workloads", {}).values() if w]:
-            if r and r.get("achieved") and job.copy_bw["GBps"] > 0:
-                r["frac_of_copy_bw"] = r["achieved"] / job.copy_bw["GBps"]
+        if job.copy_bw:
+            line["copy_bw"] = job.copy_bw
+            for r in [line.get("roofline")] + [w.get("roofline") for w in line.get("extras", {}).get("workloads", {}).values() if w]:
+                if r and r.get("achieved") and job.copy_bw["GBps"] > 0:
+                    r["frac_of_copy_bw"] = r["achieved"] / job.copy_bw["GBps"]
         # every workload's full entry is its own stdout line, the complete object goes to disk, the LAST line is the compact contract line
         for k, w in line.get("extras", {}).get("workloads", {}).items():
             if w:
                 print(json.dumps({"workload_entry": k, **w}), flush=True)
-        path = write_full(line, args.workload + (f"_n{world}" if world > 1 else ""))
+        path = write_full(line, args.workload + (f"_n{world}" if world > 1 else "")) if args.full else None
         print(json.dumps(compact_line(line, path)), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/scripts/show_bench.py <bench line json> — the default bench line as a table (headline + extras.workloads)."""
+"""profiles/scripts/show_bench.py <bench line json> — the line of a `bench.py --full` run as a table (headline + extras.workloads)."""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d["roofline"]

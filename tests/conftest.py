@@ -1,4 +1,6 @@
+import glob
 import gzip
+import io
 import os
 import sys
 
@@ -19,10 +21,22 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
+def open_golden(name):
+    """A fixture of tests/golden/ as a binary file object. One above the repository's 1 MiB limit per file is stored as byte-wise
+    parts <name>.00, <name>.01, ... whose concatenation is the original file."""
+    path = os.path.join(GOLDEN, name)
+    if os.path.exists(path):
+        return open(path, "rb")
+    parts = sorted(glob.glob(glob.escape(path) + ".[0-9][0-9]"))
+    if not parts:
+        raise FileNotFoundError(path)
+    return io.BytesIO(b"".join(open(p, "rb").read() for p in parts))
+
+
 def load_fasta_first_record(name):
     """Same behaviour as the reference's tests/fasta.py parser for the first record (test_ani.py:16-19)."""
     seq, started = [], False
-    with gzip.open(os.path.join(GOLDEN, name), "rt") as f:
+    with gzip.open(open_golden(name), "rt") as f:
         for line in f:
             if line.startswith(">"):
                 if started:

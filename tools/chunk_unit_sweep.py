@@ -33,6 +33,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools.dump_pyskani_goldens import open_fixture  # noqa: E402      (fixtures above 1 MiB are stored in parts)
 HERE = os.path.dirname(os.path.abspath(__file__))
 KAT = {"af_ref": 0.9246, "af_query": 0.9189, "mean": 0.9946, "median": 0.9995}      # test_ani.py:35-40, 56-61
 K, CC, FRAG = 15, 125, 20000
@@ -59,7 +60,7 @@ def build():
 
 def first_record(name):
     seq, started = [], False
-    with gzip.open(os.path.join(ROOT, "tests", "golden", name), "rt") as f:
+    with gzip.open(open_fixture(os.path.join(ROOT, "tests", "golden", name)), "rt") as f:
         for line in f:
             if line.startswith(">"):
                 if started:
