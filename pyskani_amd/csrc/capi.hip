@@ -21,7 +21,7 @@ struct HitBlocks {
     std::mutex mu;
     std::unordered_map<void*, size_t> live;
     void* kept = nullptr; size_t kept_bytes = 0;
-    const bool keep = !(getenv("PSK_HIT_CACHE") && getenv("PSK_HIT_CACHE")[0] == '0');
+    const bool keep = !env_val("PSK_HIT_CACHE").off();
 };
 HitBlocks& hit_blocks() { static HitBlocks* hb = new HitBlocks(); return *hb; }      // never destroyed: psk_free may run during process exit
 }
@@ -89,7 +89,7 @@ psk_status psk_ctx_create(int device, psk_ctx** out) {
     PSK_HIP(hipSetDevice(device));
     psk_ctx* c = new psk_ctx();
     c->device = device;
-    if (const char* ml = getenv("PSK_LANES")) c->max_lanes = std::max(1, std::min(16, atoi(ml)));
+    if (const EnvVal ml = env_val("PSK_LANES"); ml.text) c->max_lanes = std::max(1, std::min(16, (int)ml.num(0)));
     { LaneGuard first(c); if (!first.lane) { delete c; psk_set_error("hipStreamCreate failed"); return PSK_EHIP; } }   // the first lane exists from the start
     *out = c;
     return PSK_OK;
@@ -658,11 +658,10 @@ static psk_status ingest_impl(psk_ctx* ctx, Lane* lane, const psk_params* p, con
                 g_ingest.erase(ctx);
                 return irc;
             }
-            const char* env = getenv("PSK_INGEST_THREADS");
             // (measured on the 256-thread MI355X hosts, 1 000 x 5 Mb genomes: packed ingest 33.2 k genomes/s with 8 workers, 28.1 k with 16, 26.8 k with 32, 21.0 k with 64 -
             // more workers only contend for the memory controllers; the plain ASCII copy is PCIe-bound at 8.4-8.9 k whatever the count: profiles/r4/r4d_ingest_threads.txt)
             const unsigned hw = std::thread::hardware_concurrency();
-            int nt = env ? atoi(env) : (int)std::min(8u, std::max(1u, hw / 2));
+            const int nt = (int)env_val("PSK_INGEST_THREADS").num(std::min(8u, std::max(1u, hw / 2)));
             fresh->pool.reset(new ParallelFor(std::max(0, nt - 1)));
             slot = fresh;
         }
@@ -679,8 +678,8 @@ static psk_status ingest_impl(psk_ctx* ctx, Lane* lane, const psk_params* p, con
     {
         uint64_t ascii_total = 0, tiles_total = 0;
         for (uint32_t c = 0; c < n_contigs; c++) if (lens[c] >= MIN_LENGTH_CONTIG) { ascii_total += lens[c]; tiles_total += tiles_of(c); }
-        const char* pe = getenv("PSK_INGEST_PACKED");
-        packed = pe ? pe[0] == '1' : tiles_total * (uint64_t)(4 * TILE_WORDS) * 2 <= ascii_total;
+        const int pe = env_val("PSK_INGEST_PACKED").force();
+        packed = pe >= 0 ? pe == 1 : tiles_total * (uint64_t)(4 * TILE_WORDS) * 2 <= ascii_total;
     }
     constexpr uint64_t TILE_BYTES = 4ull * TILE_WORDS;
     // sub-batches of ~192 MB of ASCII (whole genomes; packed: ~96 MB of words = 384 MB of ASCII); device offsets of the kept contigs, 16-byte aligned

@@ -180,9 +180,9 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
     if (wide) hipLaunchKernelGGL(anchor_count_kernel, dim3(gi), dim3(256), 0, st, L.pairs, L.sbase, n_pairs, (uint32_t)n_items, L.lbcnt, L.bsum, L.blk_pair);
     const uint32_t gi4 = (gi + JT - 1) / JT;
     uint32_t n_sum = gi;
-    const char* jp_env = sw.join_pairs.get();      // "1" / "0" force / forbid the pair-major join (tests, A/B)
+    const int jp_force = sw.join_pairs.force();      // "1" / "0" force / forbid the pair-major join (tests, A/B)
     const bool gsi_join = !wide && (L.g_key || L.b_key) && L.d_pass && L.n_bq;      // (the PLAN decides - PSK_GSI_JOIN is read there, once per round: the round's sketches carry no k-mer index to fall back on)      // (every batch of a round that was planned for it: its sketches carry no k-mer index)
-    const bool join_pairs = !wide && (gsi_join || (jp_env ? jp_env[0] == '1' : (n_pairs >= 16384 && n_items / n_pairs < 2048)));
+    const bool join_pairs = !wide && (gsi_join || (jp_force >= 0 ? jp_force == 1 : (n_pairs >= 16384 && n_items / n_pairs < 2048)));
     const bool gsl = gsi_join && L.gsi_slice;      // one wave per (query, slice of its seeds): count walk -> scan over the pairs -> heads -> emit walk
     const bool gsi_one = gsi_join && !gsl && L.gsi_onepass && cap >= n_items + n_items / 8 + 8 * ((size_t)n_pairs + 1);      // (gsi_room_kernel's layout fits)
     bool probe_local = false;
@@ -190,7 +190,7 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
     GslArgs GL{};
     // (the contig join's pass bitset in LDS: the query's whole row where a wave may walk the database-wide index, the four words of one block where only blocks are walked)
     const uint32_t gsi_nw = (L.g_key && !L.gsi_slice) ? std::max(4u, (L.n_refs + 63u) / 64u) : 4u;      // (never fewer than one block's four words: a wave of the same launch may walk blocks)
-    const size_t gsi_lds_row = 8 * (size_t)gsi_nw + 4 * (size_t)((gsi_nw + 1u) & ~1u), gsi_lds_count = gsi_lds_row + 4 * (size_t)L.p_cap, gsi_lds_emit = gsi_lds_row + 4 * (size_t)L.p_cap * 5;
+    const size_t gsi_lds_row = 8 * (size_t)gsi_nw + 4 * (size_t)((gsi_nw + 1u) & ~1u), gsi_lds_count = gsi_lds_row + 4 * (size_t)L.p_cap, gsi_lds_emit = gsi_lds_row + 4 * (size_t)L.p_cap * 9;
     if (gsi_join) {
         GA.bq = L.bq; GA.pass = L.d_pass; GA.n_refs = L.n_refs; GA.qd = d_qd; GA.g_key = L.g_key; GA.g_val = L.g_val; GA.g_bucket = L.g_bucket; GA.g_shift = L.g_shift;
         GA.b_key = L.b_key; GA.b_val = L.b_val; GA.b_bucket = L.b_bucket; GA.b_shift = L.b_shift; GA.b_nb1 = L.b_nb1; GA.b_blocks = L.b_blocks; GA.b_max = L.b_max;
@@ -211,7 +211,6 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
             GL.bq = L.bq; GL.n_entries = L.n_bq; GL.tab = L.gsl_tab; GL.n_tab = L.gsl_n_tab; GL.ebase = L.gsl_ebase; GL.pass = L.d_pass; GL.n_refs = L.n_refs; GL.qd = d_qd;
             GL.g_key = L.g_key; GL.g_val = L.g_val; GL.g_bucket = L.g_bucket; GL.g_shift = L.g_shift; GL.g_nb1 = L.g_nb1; GL.g_blocks = L.g_blocks; GL.g_base = L.g_base; GL.blk_tab = d_btab; GL.blk_cnt = d_bcnt; GL.blk_cap = bcap; GL.cnt = L.gsl_cnt; GL.rec = L.gsl_rec; GL.bm = L.gsl_bm; GL.un = L.gsl_un; GL.n_slices = L.gsl_n_slices;
             GL.pair_cnt = L.big_list; GL.pstart = L.pstart; GL.cap = (uint32_t)cap; GL.err = L.misc; GL.p_cap = L.p_cap; GL.chunks = L.chunks; GL.n_chunks = L.nch;
-            { const char* e = sw.gsl_stage.get(); GL.stage = e ? atoi(e) : 1; }      // (A/B: every anchor its own 16-byte store)
             PSK_HIP(hipMemsetAsync(L.big_list, 0, 4 * ((size_t)n_pairs + 1), st));      // the slices of a pair add their counts
             PSK_TRY(gsl_count_launch(GL, st));
         }
@@ -231,23 +230,21 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
         PSK_HIP(hipcub::DeviceRadixSort::SortPairs(ctx->q_g.p, ts, keys_in, keys_out, vals_in, order, (int)n_pairs, 0, 32, st));
         const uint32_t nb = (n_pairs + 3) / 4;
         // every reference of the batch carries a probe table (ensure_probe): one line read per lookup instead of the index's chain of reads
-        // (the probe join leaves offsets within the pair + pair totals: PSK_PROBE_LOCAL=0 keeps the scan over all items; tests, A/B)
-        const bool pl_off = sw.probe_local.get() && sw.probe_local.get()[0] == '0';
-        probe_local = probe_ok && !pl_off;
-        if (probe_ok) hipLaunchKernelGGL(anchor_join_probe_kernel, dim3(nb), dim3(256), 0, st, L.pairs, L.sbase, order, n_pairs, L.lbcnt, L.bsum, L.misc + 5,
-                                         probe_local ? L.aoff : (uint32_t*)nullptr, probe_local ? L.big_list : (uint32_t*)nullptr);      // (big_list: free until select runs)
+        // (the probe join leaves offsets within the pair + pair totals)
+        probe_local = probe_ok;
+        if (probe_ok) hipLaunchKernelGGL(anchor_join_probe_kernel, dim3(nb), dim3(256), 0, st, L.pairs, L.sbase, order, n_pairs, L.lbcnt, L.bsum, L.misc + 5, L.aoff, L.big_list);      // (big_list: free until select runs)
         else hipLaunchKernelGGL(anchor_join_pairs_kernel, dim3(nb), dim3(256), 0, st, L.pairs, L.sbase, order, n_pairs, L.lbcnt, L.bsum, L.misc + 5);
         n_sum = nb;
     }
     // many mid-sized pairs (all-vs-all): the join counts every pair's anchors, one workgroup per pair then emits with a running offset
     // (anchor_emit_pairs_kernel) instead of a scan over all items; PSK_EMIT_PAIRS=1 / 0 force / forbid it (tests, A/B)
-    const char* ep_env = sw.emit_pairs.get();
+    const int ep_force = sw.emit_pairs.force();
     const bool emit_pairs = !wide && !join_pairs && n_items >= 2 * ((size_t)n_pairs + 1) &&      // (its 64-bit pair offsets live in the per-item offsets array)
-                            (ep_env ? ep_env[0] == '1' : (n_pairs >= 1024 && n_items / n_pairs >= 1024 && n_items / n_pairs <= (1u << 17)));
+                            (ep_force >= 0 ? ep_force == 1 : (n_pairs >= 1024 && n_items / n_pairs >= 1024 && n_items / n_pairs <= (1u << 17)));
     uint32_t* pair_cnt = L.live;      // free until the live list is built
     if (emit_pairs) PSK_HIP(hipMemsetAsync(pair_cnt, 0, 4 * ((size_t)n_pairs + 1), st));
     // workgroups of one pair per XCD turn (0 = contiguous eighths of the grid; PSK_XCD_GROUP overrides): see xcd_group_block_id
-    const int xg_env = sw.xcd_group.get() ? atoi(sw.xcd_group.get()) : -1;
+    const int xg_env = (int)sw.xcd_group.num(-1);
     const uint32_t xcd_group = xg_env >= 0 ? (uint32_t)xg_env : (n_pairs >= 64 ? (uint32_t)std::min<size_t>(4096, std::max<size_t>(1, 4 * (n_items / n_pairs) / (JT * 256))) : 0u);      // four pairs per turn (measured: 1 pair 38.5, 2: 37.4, 4 and more: 36.8 ms of join per 10^5 pairs; contiguous eighths: 44.0)
     if (!wide && !join_pairs) { hipLaunchKernelGGL(anchor_join4_kernel, dim3(gi4), dim3(256), 0, st, L.pairs, L.sbase, n_pairs, (uint32_t)n_items, gi, L.lbcnt, L.bsum, L.misc + 5, L.blk_pair, emit_pairs ? pair_cnt : (uint32_t*)nullptr, xcd_group); n_sum = gi4; }
     ctx->t_end();
@@ -314,16 +311,12 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
     A.out = L.cout; A.two_c = 2u * (uint32_t)prm.c; A.force_serial = force_serial; A.stats = L.misc + 1;
     A.band = std::max(1, std::min(MAX_CHAIN_BAND, BP_CHAIN_BAND / (int)prm.c));
     A.cap = (uint32_t)cap;
-    { const char* e = sw.dp_prune.get(); A.dp_prune = e && e[0] == '0' ? 0 : 1; }      // (read per call: tests switch it within a process)
     // the per-pair emit also writes the chunk table unless the pointer-chase builder is asked for (PSK_CHUNK_HOPS) or PSK_EMIT_HEADS=0
-    const char* hops_env = sw.chunk_hops.get();
-    const bool use_hops = gsi_join ? false : hops_env ? hops_env[0] != '0' : ((n_pairs < 1024 && n_items / n_pairs > 4096) || n_items / n_pairs > (1u << 20));      // (few pairs of a contig's few hundred seeds: one wave per pair walks its heads - one launch instead of two)
-    const bool emit_heads_off = sw.emit_heads.get() && sw.emit_heads.get()[0] == '0';
-    const bool emit_heads = emit_pairs && !use_hops && !emit_heads_off;
+    const bool use_hops = gsi_join ? false : sw.chunk_hops.get() ? !sw.chunk_hops.off() : ((n_pairs < 1024 && n_items / n_pairs > 4096) || n_items / n_pairs > (1u << 20));      // (few pairs of a contig's few hundred seeds: one wave per pair walks its heads - one launch instead of two)
+    const bool emit_heads = emit_pairs && !use_hops && !sw.emit_heads.off();
     // Gb-scale pairs: the walk in ITEM space where the join left per-item offsets (chunk_hops_items_kernel); PSK_HOPS_ITEMS=1 / 0 force / forbid (tests, A/B)
-    const char* hi_env = sw.hops_items.get();
-    const bool hops_items = use_hops && !gsl && !emit_pairs && !join_pairs && !sw.hops_unsliced.get() && n_items <= 0x7FFFFFFFull &&
-                            (hi_env ? hi_env[0] == '1' : n_items / n_pairs > (1u << 20));
+    const int hi_force = sw.hops_items.force();
+    const bool hops_items = use_hops && !gsl && !emit_pairs && !join_pairs && n_items <= 0x7FFFFFFFull && (hi_force >= 0 ? hi_force == 1 : n_items / n_pairs > (1u << 20));
     ctx->t_begin(K_ANCHOR_EMIT);      // anchors out of the join's records + the chunk table
     if (hops_items) {
         // ... on the lane's SIDE stream, beside the emit: the walk is a few hundred waves each waiting on its own chain of LDS round trips (24 contigs x 11 pairs: 4 ms
@@ -342,15 +335,14 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
     }
     if (gsl) { GL.anc = anc; PSK_TRY(gsl_heads_launch(GL, st)); PSK_TRY(gsl_emit_launch(GL, st)); }
     else if (gsi_join) { GA.anc = anc; GA.chunks = L.chunks; GA.n_chunks = L.nch; GA.onepass = gsi_one ? 1 : 0; GA.total = L.total; if (gsi_one) GA.pair_cnt = L.aoff;      /* (the per-item offsets array: not used by this join) */
-                    { const char* e = sw.gsi_stage.get(); GA.stage = e && e[0] == '0' ? 0 : 1; }      // (read per batch: tests switch it within a process)
-                    hipLaunchKernelGGL(gsi_join_kernel<true>, dim3(L.n_bq), dim3(64), gsi_lds_emit + (GA.stage ? 16 * (size_t)L.p_cap : 0), st, GA); }
+                    hipLaunchKernelGGL(gsi_join_kernel<true>, dim3(L.n_bq), dim3(64), gsi_lds_emit, st, GA); }
     else if (wide) hipLaunchKernelGGL(anchor_emit_kernel, dim3(gi), dim3(256), 0, st, L.pairs, L.sbase, n_pairs, (uint32_t)n_items, L.lbcnt, L.aoff, anc, (uint32_t)cap, L.misc, L.blk_pair);
     else if (emit_pairs) hipLaunchKernelGGL(anchor_emit_pairs_kernel, dim3(n_pairs), dim3(EP_T), 0, st, L.pairs, L.sbase, n_pairs, L.lbcnt, poff, anc, (uint32_t)cap, L.misc,
                                             L.cbase, emit_heads ? L.chunks : (uint2*)nullptr, L.nch);
     else {
         // k-mers with many matches (Gb-scale pairs): anchor-major emit; PSK_EMIT_EXPAND=1 / 0 force / forbid (tests, A/B)
-        const char* ex_env = sw.emit_expand.get();
-        const bool expand = ex_env ? ex_env[0] == '1' : n_items / n_pairs > (1u << 20);
+        const int ex_force = sw.emit_expand.force();
+        const bool expand = ex_force >= 0 ? ex_force == 1 : n_items / n_pairs > (1u << 20);
         if (expand) hipLaunchKernelGGL(anchor_emit_expand_kernel, dim3(gi), dim3(256), 0, st, L.pairs, L.sbase, n_pairs, (uint32_t)n_items, L.lbcnt, L.aoff, anc, (uint32_t)cap, L.misc, L.blk_pair);
         else hipLaunchKernelGGL(anchor_emit_packed4_kernel, dim3(gi4), dim3(256), 0, st, L.pairs, L.sbase, n_pairs, (uint32_t)n_items, gi, L.lbcnt, L.aoff, anc, (uint32_t)cap, L.misc, L.blk_pair,
                                 probe_local ? (const uint32_t*)L.pstart : (const uint32_t*)nullptr);
@@ -364,7 +356,7 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
             hipLaunchKernelGGL(anchor_next_kernel<2>, dim3((uint32_t)((cap + 255) / 256)), dim3(256), 0, st, anc, L.pstart, n_pairs, (const uint32_t*)coarse, a_nxt);
         } else
         hipLaunchKernelGGL(anchor_next_kernel<0>, dim3((uint32_t)((cap + 255) / 256)), dim3(256), 0, st, anc, L.pstart, n_pairs, (const uint32_t*)nullptr, a_nxt);
-        if (n_items / n_pairs > (1u << 20) && !sw.hops_unsliced.get()) {      // Gb-scale pairs: HOP_SLICES waves per pair, count then write
+        if (n_items / n_pairs > (1u << 20)) {      // Gb-scale pairs: HOP_SLICES waves per pair, count then write
             const size_t o_scr = al256(4 * (size_t)n_pairs * HOP_SLICES + 256);
             PSK_TRY(ctx->q_g.reserve(o_scr + sizeof(uint2) * n_rows + 256));
             uint32_t* slice_cnt = (uint32_t*)ctx->q_g.p;
@@ -377,10 +369,9 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
         hipLaunchKernelGGL(chunk_heads_kernel, dim3(n_pairs), dim3(64), 0, st, L.pstart, anc, L.cbase, n_pairs, L.chunks, L.nch, L.misc);
     ctx->t_end();
     ctx->t_begin(K_CHAIN_CHUNK);
-    // rows by chunk length for the DP kernels that put several chunks in one wave (row_len_kernel; PSK_ROW_SORT=0: table order)
+    // rows by chunk length for the DP kernels that put several chunks in one wave (row_len_kernel)
     auto order_rows = [&]() -> psk_status {
-        const bool rs_off = sw.row_sort.get() && sw.row_sort.get()[0] == '0';
-        if (rs_off || n_rows < 4096) return PSK_OK;
+        if (n_rows < 4096) return PSK_OK;
         size_t ts = 0;
         PSK_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, ts, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n_rows, 0, 8, st));
         const size_t ob = al256(4 * n_rows);
@@ -393,23 +384,24 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
     };
     {   // lane-per-chunk DP when the band fits its register window (PSK_CHAIN_LANE=0 keeps the wave-per-chunk DP)
         const char* le = sw.chain_lane.get();
-        A.lane_dp = !force_serial && A.band <= LANE_N && !(le && le[0] == '0');
+        A.lane_dp = !force_serial && A.band <= LANE_N && !sw.chain_lane.off();
         if (A.lane_dp) {
             PSK_TRY(order_rows());
             // few rows: spread them over more waves (idle lanes cost nothing on an under-filled chip)
             uint32_t rpw = 64;
             while (rpw > 16 && n_rows / rpw < 512) rpw >>= 1;
-            if (le && atoi(le) >= 8) rpw = (uint32_t)std::min(64, atoi(le));
+            const int le_rows = (int)sw.chain_lane.num(0);      // (PSK_CHAIN_LANE=8..64: rows per wave; "q": the quad kernel)
+            if (le_rows >= 8) rpw = (uint32_t)std::min(64, le_rows);
             const uint32_t waves = (uint32_t)((n_rows + rpw - 1) / rpw);
             A.ovf_list = L.ovf; A.ovf_count = L.misc + 8;      // misc was zeroed above
-            const bool quad = le && le[0] == 'q' ? true : (le && atoi(le) >= 8 ? false : n_rows < 32 * 1024);
+            const bool quad = le && le[0] == 'q' ? true : (le_rows >= 8 ? false : n_rows < 32 * 1024);
             if (quad) {   // small launch: four lanes per chunk, 16 chunks per wave
                 const uint32_t qw = (uint32_t)((n_rows + 15) / 16);
                 hipLaunchKernelGGL(chain_quad_kernel, dim3((qw + LANE_WAVES - 1) / LANE_WAVES), dim3(64 * LANE_WAVES), 0, st, A);
             } else {
                 // Gb-scale pairs: sixteen tree slots per chunk (twelve of them in LDS); PSK_LANE_XTREES=1 / 0 force / forbid (tests, A/B)
-                const char* xt_env = sw.lane_xtrees.get();
-                const bool xtrees = xt_env ? xt_env[0] == '1' : n_items / n_pairs > (1u << 20);
+                const int xt_force = sw.lane_xtrees.force();
+                const bool xtrees = xt_force >= 0 ? xt_force == 1 : n_items / n_pairs > (1u << 20);
                 if (A.band <= 20 && xtrees) hipLaunchKernelGGL(chain_lane20x_kernel, dim3((waves + LANE_WAVES - 1) / LANE_WAVES), dim3(64 * LANE_WAVES), 0, st, A, rpw);
                 else if (A.band <= 20) hipLaunchKernelGGL(chain_lane20_kernel, dim3((waves + LANE_WAVES - 1) / LANE_WAVES), dim3(64 * LANE_WAVES), 0, st, A, rpw);
                 else hipLaunchKernelGGL(chain_lane_kernel, dim3((waves + LANE_WAVES - 1) / LANE_WAVES), dim3(64 * LANE_WAVES), 0, st, A, rpw);
@@ -421,16 +413,15 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
     }
     // bands beyond the lane kernel's window (c < 105; metagenome mode c = 30: 83): four lanes per chunk with 21-deep windows, its leftovers to
     // the wave-per-chunk kernel's list form; PSK_CHAIN_QUAD_DEEP=0 keeps the wave-per-chunk kernel for every chunk (tests, A/B)
-    const bool qd_off = sw.chain_quad_deep.get() && sw.chain_quad_deep.get()[0] == '0';
     // a launch of few rows is as slow as its longest chunk: one wave per row with the window in registers (PSK_CHAIN_WAVE_REG=1 / 0 force / forbid: tests, A/B)
-    const char* wr_env = sw.chain_wave_reg.get();
-    const bool wave_reg = !A.lane_dp && !force_serial && A.band < 128 && (wr_env ? wr_env[0] == '1' : n_rows <= 2048);      // (one wave per SIMD up to 1 024 rows: 0.29 us per anchor of the longest chunk; the four-lanes-per-chunk kernel needs 0.9 us but takes 16 rows per wave)
+    const int wr_force = sw.chain_wave_reg.force();
+    const bool wave_reg = !A.lane_dp && !force_serial && A.band < 128 && (wr_force >= 0 ? wr_force == 1 : n_rows <= 2048);      // (one wave per SIMD up to 1 024 rows: 0.29 us per anchor of the longest chunk; the four-lanes-per-chunk kernel needs 0.9 us but takes 16 rows per wave)
     if (wave_reg) {
         const dim3 g((uint32_t)((n_rows + CHAIN_WAVES - 1) / CHAIN_WAVES)), b(64 * CHAIN_WAVES);
         if (A.band < 64) hipLaunchKernelGGL(chain_wave_reg_kernel<1>, g, b, 0, st, A);
         else hipLaunchKernelGGL(chain_wave_reg_kernel<2>, g, b, 0, st, A);
     }
-    const bool quad_deep = !wave_reg && !A.lane_dp && !force_serial && !qd_off && A.band <= 4 * QD && !(sw.chain_lane.get() && sw.chain_lane.get()[0] == '0');
+    const bool quad_deep = !wave_reg && !A.lane_dp && !force_serial && !sw.chain_quad_deep.off() && A.band <= 4 * QD && !sw.chain_lane.off();
     if (quad_deep) {
         A.ovf_list = L.ovf; A.ovf_count = L.misc + 8;      // misc was zeroed above
         A.lane_dp = 1;                                     // (chain_chunk_list_kernel walks the list)
@@ -459,8 +450,7 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
     }
     ctx->t_begin(K_SELECT);
     {   // batches of pairs with short chunk tables (contigs): one lane per pair first; PSK_SELECT_TINY=0 leaves every pair to the wave kernels
-        const bool tiny_off = sw.select_tiny.get() && sw.select_tiny.get()[0] == '0';
-        SA.tiny_done = use_live && !force_serial && !tiny_off && n_rows / n_pairs < 16;
+        SA.tiny_done = use_live && !force_serial && !sw.select_tiny.off() && n_rows / n_pairs < 16;
         SA.rest_list = (uint32_t*)L.hits_sel; SA.rest_count = L.misc + 13;      // (hits_sel: free until the hits are selected; misc was zeroed by pair_table_kernel)
         if (SA.tiny_done) hipLaunchKernelGGL(select_tiny_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, SA);
     }
@@ -477,7 +467,7 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
             BA.conf = (uint8_t*)(U + 7 * na);
             BA.parts = (uint32_t*)(E + (((size_t)na * (8 + 4 * 7 + 1) + 255) & ~(size_t)255));
             BA.huge_list = L.huge_list; BA.huge_count = L.misc + 11; BA.ctr = L.misc + 32; BA.huge_c = BA.parts + (size_t)2 * BIG_GMAX * (BIG_GROUPS + 64);
-            const uint32_t solo = sw.big_solo.get() ? (uint32_t)std::max(atoi(sw.big_solo.get()), CMAX) : BIG_SOLO;
+            const uint32_t solo = sw.big_solo.get() ? (uint32_t)std::max((int)sw.big_solo.num(0), CMAX) : BIG_SOLO;
             BA.solo = solo;
             hipLaunchKernelGGL(select_big_kernel, dim3(std::min<uint32_t>(n_pairs, 64u)), dim3(BIG_T), 0, st, BA);
             // the cooperative launch only where a pair can have more than BIG_SOLO candidates (a candidate needs 3 anchors; there are
@@ -498,14 +488,14 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
                         int per_cu = 0, cus = 0;
                         PSK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, select_huge_kernel, BIG_T, 0));
                         PSK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-                        if (const char* e = sw.huge_slots.get()) { per_cu = 1; cus = std::max(0, atoi(e)); }      // tests: pretend a smaller device
+                        if (sw.huge_slots.get()) { per_cu = 1; cus = std::max(0, (int)sw.huge_slots.num(0)); }      // tests: pretend a smaller device
                         it = slots_of.emplace(ctx->device, (uint32_t)std::max(0, per_cu) * (uint32_t)std::max(0, cus)).first;
                     }
                     slots = it->second;
                 }
                 uint32_t nb = BIG_GMAX;
-                const char* hm_env = sw.huge_min_seeds.get();      // (tests: batches of small pairs take the full-size launch and its mutex too)
-                if (n_items / n_pairs > (hm_env ? strtoull(hm_env, nullptr, 10) : (1ull << 20))) {      // the device's one full-size launch: the largest power of two that is resident at once
+                // (PSK_HUGE_MIN_SEEDS, tests: batches of small pairs take the full-size launch and its mutex too)
+                if ((double)(n_items / n_pairs) > sw.huge_min_seeds.num((double)(1ull << 20))) {      // the device's one full-size launch: the largest power of two that is resident at once
                     ctx->huge_acquire();
                     while (nb > 1 && nb > slots) nb >>= 1;
                 } else {                                     // a share of what the full-size launch leaves, safe if every lane launched at once
@@ -531,15 +521,14 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
     R.live = use_live ? L.live : nullptr; R.n_live = L.misc + 9;
     if (use_live) hipLaunchKernelGGL(pair_empty_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, R, n_pairs);
     // many pairs with short chunk tables (contigs): one wave per pair first; the workgroup-per-pair kernel then only sees the long tables
-    const char* rs_env = sw.reduce_small.get();
-    const bool no_small = rs_env && rs_env[0] == '0';
+    const bool no_small = sw.reduce_small.off();
     // tables of 65 .. 512 rows (pairs of ~5 Mb genomes: ~250): one wave per pair, eight rows per lane; PSK_REDUCE_WAVE=0 leaves them to the workgroup kernel (tests, A/B)
-    const bool no_wave = sw.reduce_wave.get() && sw.reduce_wave.get()[0] == '0';
+    const bool no_wave = sw.reduce_wave.off();
     R.wave_done = !no_wave && !no_small && L.rows_pair_max > 64u && n_rows / n_pairs <= 64u * RW_PER;
     // tables of <= 64 rows (contigs; the short pairs beside the others): one wave per pair, a row per lane (also without the live list: the few pairs of one contig's query)
     R.small_done = !no_small && (n_rows / n_pairs < 16 || R.wave_done);
     // contig batches with the mean ANI: pairs of up to four chunk rows by one lane each first (PSK_REDUCE_TINY=0: by a wave each)
-    const bool no_tiny = sw.reduce_tiny.get() && sw.reduce_tiny.get()[0] == '0';
+    const bool no_tiny = sw.reduce_tiny.off();
     R.tiny_done = R.small_done && !no_tiny && !o->median && !o->robust && n_rows / n_pairs < 16;
     if (R.tiny_done) hipLaunchKernelGGL(pair_reduce_tiny_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, R, n_pairs);
     if (R.small_done) hipLaunchKernelGGL(pair_reduce_small_kernel, dim3(std::min<uint32_t>((n_pairs + 3) / 4, 8192u)), dim3(256), 0, st, R, n_pairs);

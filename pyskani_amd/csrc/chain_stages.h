@@ -82,7 +82,6 @@ struct ChainArgs {
     Strided<int32_t> c_score; Strided<uint32_t> c_q0, c_q1, c_r0, c_r1, c_n, c_state, c_rc;   // candidate chains, chunk s writes at [s, s + n_cand): fields of 32-byte records
     uint32_t two_c; int band; int force_serial; int lane_dp;
     uint32_t cap;      // anchors the arrays hold (chunk_seeds_kernel's bound on what a chunk row may point at)
-    int dp_prune;      // the lane / quad DP kernels score the far part of the band only where it could win ($PSK_DP_PRUNE=0: always)
     uint32_t* ovf_list; uint32_t* ovf_count;   // rows the lane kernel hands to the wave kernel (more than LANE_TREES qualifying chain trees, >= 16 384 anchors)
     uint32_t* stats;   // [1] chunks / [3] pairs that took a serial fallback (rare paths only: a counter every wave bumps
                        // serialises the whole launch on one L2 address)
@@ -191,7 +190,6 @@ struct GsiJoinArgs {
     // eight more), the walk leaves every pair's count in pair_cnt and adds the batch's total to *total; a pair that would need more room (a reference that
     // holds the query's k-mers several times over) raises err bit 2 and the batch is rerun with the two passes
     int onepass; unsigned long long* total;
-    int stage;      // EMIT: anchors leave in pairs of 32 bytes (an even-indexed anchor waits in LDS for its neighbour); 0: every anchor its own 16-byte store ($PSK_GSI_STAGE=0)
 };
 
 #ifndef LANE_NEAR_N

@@ -19,6 +19,15 @@
 #include <vector>
 #include "../../include/pyskani_amd.h"
 
+// ---- a $PSK_* switch's text (nullptr: not set), read the three ways the switches are read (env_val: one getenv per read)
+struct EnvVal {
+    const char* text;
+    bool off() const { return text && text[0] == '0'; }                 // set and starting with '0'
+    int force() const { return text ? text[0] == '1' : -1; }           // -1: not set; 1: starts with '1'; 0: anything else
+    double num(double dflt) const { return text ? atof(text) : dflt; }
+};
+static inline EnvVal env_val(const char* name) { return EnvVal{getenv(name)}; }
+
 // ---- algorithm constants (normative definition: oracle/skani_oracle.c) ----
 constexpr int K_MARKER = 21;
 constexpr uint32_t MIN_LENGTH_CONTIG = 500;  // lib.rs:156
@@ -176,11 +185,8 @@ struct Lane {
     }
     void t_end(hipStream_t st = nullptr) { if (dev->timing && !pending.empty()) (void)hipEventRecord(pending.back().b, st ? st : stream); }
     psk_status pool_alloc(size_t bytes, void** out, size_t* got) { return dev->pool_alloc(bytes, out, got); }
-    // resources of one in-flight sketch sub-batch: own stream + scratch, so that sketch_emit / sorts of
-    // sub-batch j overlap sketch_scan of sub-batch j+1
-    struct JobRes {
-        hipStream_t stream = nullptr; bool own_stream = false;
-        hipEvent_t scan_done = nullptr;
+    // scratch and pinned staging of the sketch pipeline (sketch.hip: SketchJob)
+    struct SketchRes {
         Scratch s_desc, s_packed, s_mask, s_counts, s_offs, s_tmp, s_mark, s_slices;
         void* pinned = nullptr; size_t pinned_cap = 0;
         psk_status pin(size_t bytes, void** out) {
@@ -195,28 +201,12 @@ struct Lane {
             return PSK_OK;
         }
     };
-    std::vector<JobRes*> jobs;
-    psk_status job(size_t j, JobRes** out) {
-        while (jobs.size() <= j) {
-            JobRes* r = new JobRes();
-            if (jobs.empty()) r->stream = stream;
-            else { PSK_HIP(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking)); r->own_stream = true; }
-            PSK_HIP(hipEventCreateWithFlags(&r->scan_done, hipEventDisableTiming));
-            jobs.push_back(r);
-        }
-        *out = jobs[j];
-        return PSK_OK;
-    }
-    void jobs_release() {
-        for (JobRes* r : jobs) {
-            Scratch* all[] = {&r->s_desc, &r->s_packed, &r->s_mask, &r->s_counts, &r->s_offs, &r->s_tmp, &r->s_mark, &r->s_slices};
-            for (Scratch* s : all) s->release();
-            if (r->pinned) (void)hipHostFree(r->pinned);
-            if (r->scan_done) (void)hipEventDestroy(r->scan_done);
-            if (r->own_stream) (void)hipStreamDestroy(r->stream);
-            delete r;
-        }
-        jobs.clear();
+    SketchRes sk;
+    void sk_release() {
+        Scratch* all[] = {&sk.s_desc, &sk.s_packed, &sk.s_mask, &sk.s_counts, &sk.s_offs, &sk.s_tmp, &sk.s_mark, &sk.s_slices};
+        for (Scratch* s : all) s->release();
+        if (sk.pinned) (void)hipHostFree(sk.pinned);
+        sk.pinned = nullptr; sk.pinned_cap = 0;
     }
     Scratch s_desc, s_packed, s_mask, s_counts, s_offs, s_tmp, s_mark, s_flags, s_misc;  // sketch
     Scratch q_a, q_b, q_c, q_d, q_e, q_f, q_g, q_h, q_i;                                  // query
@@ -242,7 +232,7 @@ struct Lane {
         if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); copy_stream = nullptr; }
         if (side_stream) { (void)hipStreamSynchronize(side_stream); (void)hipStreamDestroy(side_stream); side_stream = nullptr; if (side_fork) (void)hipEventDestroy(side_fork); if (side_join) (void)hipEventDestroy(side_join); side_fork = side_join = nullptr; }
         for (Scratch* s : all) s->release();
-        jobs_release();
+        sk_release();
         if (h_pinned) (void)hipHostFree(h_pinned);
         h_pinned = nullptr; h_pinned_cap = 0;
         for (TimerRec& r : pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }

@@ -101,7 +101,7 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
     // reaches the largest far f + ANCHOR_SCORE2 is done; and an anchor whose diagonal is not within MAX_GAP_LENGTH of any far entry's (far_diag: one bit
     // per 1024 diagonals mod 32, two bits per entry, rebuilt every 16 steps) has no far predecessor at all - the chance match off the chain. The wave
     // decides: one lane that needs the far part has all 64 score it (same results). Not for the Gb-scale kernel (XT: most anchors there are chance matches).
-    const bool prune = XT == 0 && A.dp_prune != 0;
+    constexpr bool prune = XT == 0;
     constexpr int NR = LANE_NEAR;
     uint32_t far_diag = 0;
     for (uint32_t tb = 0; __any(tb < len); tb += 4 * LD) {
@@ -417,7 +417,6 @@ __global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_deep_kernel(ChainA
     bool ovf = false;
     uint32_t (*rd)[16] = s_rd[wave];
     const int32_t bj = A.band + j;
-    const bool prune = A.dp_prune != 0;
     uint32_t far_diag = 0;
     for (uint32_t t0 = 0; __any(t0 < len); t0 += 4) {
         const uint32_t x0 = s_al + t0;
@@ -430,14 +429,14 @@ __global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_deep_kernel(ChainA
         // the largest f - 1 among the far entries of the quad (-1: all empty), one pass per step (the window does not move within a step). Along a chain f
         // grows by ~ANCHOR_SCORE2 per anchor, so the nearest predecessors nearly always beat that bound and the far three quarters of the band are not scored
         // at all; the decision is taken per WAVE (an anchor off its chunk's chain - no near predecessor - has all sixteen quads score everything: same
-        // results, nothing skipped). $PSK_DP_PRUNE=0: every entry always (tests, A/B).
+        // results, nothing skipped).
         // ... and only for an anchor whose diagonal is within MAX_GAP_LENGTH of a far entry's. far_diag: one bit per 1024 diagonals (mod 32): an entry on diagonal
         // d sets the two bits that cover d - MAX_GAP_LENGTH .. d + MAX_GAP_LENGTH; an anchor whose own bit is clear has no predecessor in the far part. That
         // is the chance match off the chunk's chain (k-mers are seeds by content: ~1 % of a query's seeds also sit somewhere else in a 5 Mb reference): no
         // near predecessor either, but no reason to score 60 entries that cannot hold one. The bits of the entry that turns far are added every step and
         // the set is rebuilt every 16 steps (bits of entries that left linger until then: a few more anchors pass the test, none fewer).
         int32_t far_top = -1;
-        if (prune) {
+        {
             if ((t0 & 63u) == 0) {
                 far_diag = 0;
 #pragma unroll
@@ -467,8 +466,8 @@ __global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_deep_kernel(ChainA
                 const int32_t k = quad_eval(qx, ux, mx, late ? nq : Wq[QD - 1], late ? nu : Wu[QD - 1], late ? nm : Wm[QD - 1], late ? nf : Wf[QD - 1], late ? u : u + 4 * QD, bj);
                 best = k > best ? k : best;
             }
-            bool far = !prune;
-            if (prune) {      // does any quad of the wave still need its far entries? (best, before the lane's + j: score << 7 | low bits)
+            bool far;
+            {      // does any quad of the wave still need its far entries? (best, before the lane's + j: score << 7 | low bits)
                 int32_t nb = best;
                 int32_t o = __builtin_amdgcn_mov_dpp(nb, 0xB1, 0xF, 0xF, true); nb = o > nb ? o : nb;
                 o = __builtin_amdgcn_mov_dpp(nb, 0x4E, 0xF, 0xF, true); nb = o > nb ? o : nb;

@@ -376,7 +376,7 @@ __global__ __launch_bounds__(256) void anchor_join_probe_kernel(const PairDesc* 
         const ProbeLine* __restrict__ tab = P.r_tab;
         const uint32_t* __restrict__ q_kmer = P.q_kmer;
         uint2* __restrict__ out = item_out + sbase[p];
-        uint32_t* __restrict__ loc = aoff_local ? aoff_local + sbase[p] : nullptr;
+        uint32_t* __restrict__ loc = aoff_local + sbase[p];
         uint32_t run = 0;      // anchors of the pair before the items of this step
         constexpr int U = 4;
         for (uint32_t j0 = 0; j0 < qn; j0 += 64 * U) {
@@ -405,20 +405,18 @@ __global__ __launch_bounds__(256) void anchor_join_probe_kernel(const PairDesc* 
                 out[j] = rec[u];
                 total += c;
             }
-            if (loc) {
 #pragma unroll
-                for (int u = 0; u < U; u++) {
-                    const uint32_t j = j0 + u * 64 + lane;
-                    const uint32_t c = j < qn ? rec[u].y >> 24 : 0u;
-                    uint32_t incl = c;
+            for (int u = 0; u < U; u++) {
+                const uint32_t j = j0 + u * 64 + lane;
+                const uint32_t c = j < qn ? rec[u].y >> 24 : 0u;
+                uint32_t incl = c;
 #pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o); if (lane >= o) incl += v; }
-                    if (j < qn) loc[j] = run + incl - c;
-                    run += __shfl(incl, 63);
-                }
+                for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o); if (lane >= o) incl += v; }
+                if (j < qn) loc[j] = run + incl - c;
+                run += __shfl(incl, 63);
             }
         }
-        if (pair_cnt && lane == 0) pair_cnt[p] = run;
+        if (lane == 0) pair_cnt[p] = run;
     }
     block_total(total, lb, block_sum);
 }
@@ -1027,12 +1025,12 @@ __global__ __launch_bounds__(64) void gsi_join_kernel(GsiJoinArgs A) {
     const uint32_t n_blk = A.b_blocks ? A.blk_cnt[blockIdx.x] : 0u;
     const bool blocked = A.b_blocks && (n_blk <= A.b_max || !A.g_key);
     const uint32_t nw = blocked ? 4u : (A.n_refs + 63u) / 64u;      // words of the bitset in use (the launch's LDS holds nw_lds)
-    // LDS of the wave. EMIT: [with A.stage: the even-indexed anchor every pair holds back, 16 B per pair][the pairs' STATE, one 16-byte record each: {anchors so far, first
+    // LDS of the wave. EMIT: [the even-indexed anchor every pair holds back, 16 B per pair][the pairs' STATE, one 16-byte record each: {anchors so far, first
     // anchor of the pair (GSI_DEAD: fewer than MIN_ANCHORS anchors - it cannot chain: no anchors, no chunk table), query position of the open chunk's head, q contig << 16 | rows
     // so far}: ONE read per anchor in the walk's chain of dependent LDS round trips, where four arrays took three trips][the open chunk's first anchor per pair][the pass bitset
     // and its prefix counts]. COUNT: [bitset][prefix counts][the pairs' anchor counts].
     uint4* s_line = (uint4*)s_gsi;
-    uint4* s_st = s_line + ((EMIT && A.stage) ? A.p_cap : 0u);
+    uint4* s_st = s_line + (EMIT ? A.p_cap : 0u);
     uint32_t* s_hi = (uint32_t*)(s_st + (EMIT ? A.p_cap : 0u));
     unsigned long long* s_bits = (unsigned long long*)(s_hi + (EMIT ? A.p_cap : 0u));
     uint32_t* s_pref = (uint32_t*)(s_bits + A.nw_lds);
@@ -1163,7 +1161,7 @@ __global__ __launch_bounds__(64) void gsi_join_kernel(GsiJoinArgs A) {
                     j = valid ? (uint32_t)lane - (63u - (uint32_t)__clzll((long long)upto)) : 0u;
                 }
                 const uint32_t base = valid ? st.x : 0u;
-                // Anchors leave in PAIRS (A.stage): a scattered 16-byte store costs 32 bytes of HBM write traffic (profiles/r4/r4k_pmc_calibration.md), so an anchor
+                // Anchors leave in PAIRS: a scattered 16-byte store costs 32 bytes of HBM write traffic (profiles/r4/r4k_pmc_calibration.md), so an anchor
                 // with an even index waits in LDS (one 16-byte slot per pair) for its odd neighbour, and the lane that brings that one writes both: one 32-byte granule.
                 // Inside a group of several lanes (a reference holding the k-mer several times) neighbours go out directly; only a group's last even anchor waits.
                 bool hold = false; uint4 av = make_uint4(0, 0, 0, 0);
@@ -1174,8 +1172,7 @@ __global__ __launch_bounds__(64) void gsi_join_kernel(GsiJoinArgs A) {
                         const uint32_t rmeta = (uint32_t)((((v >> 33) & 0x7FFFull) << 1) | (v & 1ull));      // ref contig << 1 | (fwd < rc)
                         av = make_uint4(sqp, (uint32_t)(v >> 1), (rmeta & ~1u) | ((rmeta ^ sqm) & 1u), sqm >> 1);
                         const uint32_t d32 = (uint32_t)dst;
-                        if (!A.stage) A.anc[dst] = av;
-                        else if (d32 & 1u) {      // odd: out it goes - with its even neighbour from LDS when that one is the pair's own and is not the lane before this one
+                        if (d32 & 1u) {      // odd: out it goes - with its even neighbour from LDS when that one is the pair's own and is not the lane before this one
                             if (!same && d32 > st.y) A.anc[d32 - 1u] = s_line[slot];
                             A.anc[d32] = av;
                         } else if (last) hold = true;      // even and the group's last: waits (written to LDS below, after the step's reads of the slots)
@@ -1217,7 +1214,7 @@ __global__ __launch_bounds__(64) void gsi_join_kernel(GsiJoinArgs A) {
             uint32_t rows = 0;
             const uint4 fin = s_st[j];
             const uint32_t n = fin.x;
-            if (A.stage && n && fin.y != GSI_DEAD && !(A.onepass && n > nq + (nq >> 3) + 8u)) {      // an even last anchor is still waiting for a neighbour that never came
+            if (n && fin.y != GSI_DEAD && !(A.onepass && n > nq + (nq >> 3) + 8u)) {      // an even last anchor is still waiting for a neighbour that never came
                 const unsigned long long e = (unsigned long long)fin.y + n - 1u;
                 if (!(e & 1ull) && e < A.cap) A.anc[e] = s_line[j];
             }

@@ -223,7 +223,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
     const double screen_val = o->cutoff != 0.0 ? o->cutoff : 0.80;   // lib.rs:603-609
     // queries per round (pass matrix <= 1 GiB). A round costs ~3.5 ms of host work with the GPU idle (its screen set-up, the shortlist, the last batch's hits):
     // 65 536 queries per round instead of 16 384 is 2 rounds instead of 7 for 100 000 contigs (metagenome step 420 -> 384 ms); PSK_ROUND_QUERIES overrides (tests, A/B)
-    const uint32_t qb_env = sw.round_queries.get() ? (uint32_t)std::max(1, atoi(sw.round_queries.get())) : 0u;
+    const uint32_t qb_env = sw.round_queries.get() ? (uint32_t)std::max(1, (int)sw.round_queries.num(0)) : 0u;
     const uint32_t QB = std::max<uint32_t>(1, std::min<uint32_t>(qb_env ? qb_env : 65536u, (uint32_t)((1ull << 30) / n)));
     {
         const char* force = sw.screen.get();
@@ -265,8 +265,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
         PoolScratch pf_buf;      // lives until the round's synchronisations are through, like the host arrays the copies read
         std::vector<uint32_t> rq, eoff, qn;
         {
-            const char* pf_env = sw.prefilter.get();      // "0": never; "1": whatever the number of pairs (tests)
-            const bool pf_off = pf_env && pf_env[0] == '0', pf_force = pf_env && pf_env[0] == '1';
+            const bool pf_off = sw.prefilter.off(), pf_force = sw.prefilter.force() == 1;      // "0": never; "1": whatever the number of pairs (tests)
             uint64_t E = 0;
             if (!o->faster_small && !pf_off && db->params.k <= 15)
                 for (uint32_t i = 0; i < m; i++) {
@@ -279,8 +278,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
             bool refs_ok = !rq.empty() && ((uint64_t)rq.size() * n >= (pf_force ? 1ull : (1ull << 20))) && (uint64_t)rq.size() * n * 4 <= (1ull << 31);
             if (refs_ok) for (const psk_sketch* rs : db->refs) if (!rs->has_seeds || rs->params.k != db->params.k || rs->params.c != db->params.c) { refs_ok = false; break; }
             // through the database-wide seed index where the database can have one (no per-reference index, no gather, no sort); PSK_GSI_JOIN=0: the per-reference path
-            const bool gsi_pf_off = sw.gsi_join.get() && sw.gsi_join.get()[0] == '0';      // (read per call: tests switch it within a process)
-            if (refs_ok && !gsi_pf_off && !sw.join_wide()) {
+            if (refs_ok && !sw.gsi_join.off() && !sw.join_wide()) {
                 if (db->gsi_state == 0) PSK_TRY(exclusive([&]() -> psk_status { return build_gsi(ctx, db); }));
                 if (db->gsi_state != 1 && db->bsi_state == 0) PSK_TRY(exclusive([&]() -> psk_status { return build_bsi(ctx, db); }));      // (no database-wide index - more than 65 536 references -: the blocked one)
                 if (db->gsi_state == 1 || db->bsi_state == 1) {
@@ -399,25 +397,23 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
         bool round_probe = false, round_gsi = false, want_small = false, round_slice = false, round_bsi = false;
         uint64_t round_items = 0;      // (pair, query seed) items of the round
         for (uint32_t i = 0; i < m; i++) round_items += (uint64_t)h_cnt[i] * queries[b + i]->n_seeds;
-        const double max_blocks_join = sw.gsl_max_blocks.get() ? atof(sw.gsl_max_blocks.get()) : 4.0;
+        const double max_blocks_join = sw.gsl_max_blocks.num(4.0);
         {
-            const char* pb_env = sw.probe.get();
-            const bool pb_off = pb_env && pb_env[0] == '0', pb_force = pb_env && pb_env[0] == '1';
+            const bool pb_off = sw.probe.off(), pb_force = sw.probe.force() == 1;
             want_small = !pb_off && (pb_force || (round_pairs >= 16384 && round_items / round_pairs < 2048));
-            const bool gsi_join_off = sw.gsi_join.get() && sw.gsi_join.get()[0] == '0';      // (read per round: tests switch it within a process; chain_run follows the plan)
+            const bool gsi_join_off = sw.gsi_join.off();      // (read per round: tests switch it within a process; chain_run follows the plan)
             // Rounds of many MID-SIZED pairs (all-vs-all of ~5 Mb genomes: every query passes against its family) go through the same index by (query, slice) waves
             // (slice_join.hip) instead of one merge join per pair: one lookup per query SEED where the per-pair join makes one per (pair, seed). PSK_GSI_SLICE=0 never,
             // =1 whatever the round's shape (tests, A/B)
-            const char* sl_env = sw.gsi_slice.get();      // (read per round: tests switch it within a process)
-            const bool sl_off = sl_env && sl_env[0] == '0', sl_force = sl_env && sl_env[0] == '1';
+            const bool sl_off = sw.gsi_slice.off(), sl_force = sw.gsi_slice.force() == 1;
             const bool want_slice = !want_small && !sl_off && (sl_force || (round_pairs >= 2048 && round_items / round_pairs >= 2048 && round_items / round_pairs <= (1u << 18)));
-            const double max_blocks = sw.gsl_max_blocks.get() ? atof(sw.gsl_max_blocks.get()) : 4.0;
+            const double max_blocks = sw.gsl_max_blocks.num(4.0);
             uint64_t q_with = 0; for (uint32_t i = 0; i < m; i++) q_with += h_cnt[i] != 0;
             const bool few_blocks = (double)round_blocks <= max_blocks * (double)std::max<uint64_t>(q_with, 1);
             if (want_small && !gsi_join_off && !sw.join_wide()) {
                 // contigs: through the index in blocks of references when their passing references sit in few of them (a contig's relatives - what the marker screen and the
                 // prefilter of rescued contigs leave), through the database-wide index otherwise (a rescued contig against EVERY reference: one walk instead of one per block)
-                const bool bsi_small_off = sw.bsi_small.get() && sw.bsi_small.get()[0] == '0';      // (tests, A/B)
+                const bool bsi_small_off = sw.bsi_small.off();      // (tests, A/B)
                 if (db->gsi_state == 0) PSK_TRY(exclusive([&]() -> psk_status { return build_gsi(ctx, db); }));
                 round_gsi = db->gsi_state == 1;
                 if (!bsi_small_off || !round_gsi) {      // (every wave of the join chooses by its own query: both indexes are handed over; a database beyond the database-wide index's 65 536 references has the blocked one alone)
@@ -474,7 +470,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
         // pair_reduce and the batch's synchronisation are spread over four times the pairs of 2^27: all-vs-all 185 -> 169 ms);
         // 2^27 when a query is Gb-scale (~6 anchors per seed from chance 15-mer matches: 2^27 seeds already carry 14 GB of anchors).
         // A batch whose scratch cannot be allocated is planned again at a quarter of the size.
-        const int items_env = sw.batch_items_log2.get() ? std::min(31, std::max(16, atoi(sw.batch_items_log2.get()))) : 0;
+        const int items_env = sw.batch_items_log2.get() ? std::min(31, std::max(16, (int)sw.batch_items_log2.num(0))) : 0;
         int items_log2 = items_env ? items_env : 29;
         if (!items_env) for (uint32_t i = 0; i < m; i++) if (h_qd[i].n > (1u << 20)) { items_log2 = 27; break; }
         if (!items_env && items_log2 == 27) {
@@ -493,7 +489,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
         // Rounds of many small pairs (contigs): up to 2^22 pairs and 2^30 seeds per batch. The probe join visits a batch's pairs reference by reference, and a line of a
         // reference's table is probed about once per 2^20 pairs of a 5 000-reference database: with twice the pairs every line is probed twice while it is still
         // cached (join 142 -> 124 ms per 100 000 contigs). PSK_BATCH_PAIRS_LOG2 overrides (tests, A/B).
-        const int pairs_env = sw.batch_pairs_log2.get() ? std::min(24, std::max(10, atoi(sw.batch_pairs_log2.get()))) : 0;
+        const int pairs_env = sw.batch_pairs_log2.get() ? std::min(24, std::max(10, (int)sw.batch_pairs_log2.num(0))) : 0;
         if (!items_env && items_log2 == 29 && round_probe) items_log2 = 30;
         // ... and rounds of mid-sized pairs joined by (query, slice) waves: a launch of 10 000 waves is three waves deep on the chip and its last third runs half empty;
         // 2^30 seeds (268 genomes of 5 Mb and their ~27 000 pairs) per batch: 860 -> 796 ms per 10 000 x 10 000 step (2^28: 969)
@@ -501,8 +497,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
         uint64_t max_items = 1ull << items_log2, max_pairs = 1ull << (pairs_env ? pairs_env : (round_probe ? 22 : 21)), max_rows = 1ull << 26;      // (2^22 pairs: 363 -> 353 ms per 100 000 contigs)
         {   // the one-pass index join lays a batch's anchors out at 9/8 of its items (gsi_room_kernel) where about two thirds of that are used: three quarters of the
             // items per batch keep the per-anchor arrays (100 bytes per slot) near what the two passes reserved
-            const bool one_off = sw.gsi_onepass.get() && sw.gsi_onepass.get()[0] == '0';
-            if (round_gsi && !round_slice && !one_off && !items_env && max_items == (1ull << 30)) max_items = 3ull << 28;
+            if (round_gsi && !round_slice && !sw.gsi_onepass.off() && !items_env && max_items == (1ull << 30)) max_items = 3ull << 28;
         }
         uint32_t qi = 0, rank = 0;      // next (query, rank) to chain
         std::vector<uint64_t> q_hits(m, 0);            // hits per query of the round
@@ -548,8 +543,8 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                     HitRec<H>::finish(h, b + lq);
                 }
             };
-            static const unsigned move_threads = [] { const char* e = getenv("PSK_HIT_THREADS"); const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-                                                      return e ? (unsigned)std::max(1, atoi(e)) : std::min(8u, std::max(1u, hw / 8)); }();
+            static const unsigned move_threads = [] { const EnvVal e = env_val("PSK_HIT_THREADS"); const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+                                                      return e.text ? (unsigned)std::max(1, (int)e.num(0)) : std::min(8u, std::max(1u, hw / 8)); }();
             const unsigned nt = (size_t)pend_n * sizeof(H) >= ((size_t)16 << 20) ? move_threads : 1u;
             if (nt <= 1) move(0, pend_n, false);
             else {
@@ -579,7 +574,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
         // batch order; the helpers touch nothing of the database's lock. A batch that does not fit its lane (memory, too repetitive) ends the mode: the loop
         // below takes over from that batch's first pair at a quarter of the size. PSK_PIPELINE=1 / 0 force / forbid (tests, A/B).
         {
-            const int pipe_env = sw.pipeline.get() ? atoi(sw.pipeline.get()) : -1;      // (read per round: bench.py takes its kernel table from a step run as one chain)
+            const int pipe_env = (int)sw.pipeline.num(-1);      // (read per round: bench.py takes its kernel table from a step run as one chain)
             const bool pipe_want = round_slice && pipe_env != 0 && (pipe_env == 1 || round_items >= (4ull << 29));
             if (pipe_want && !lane2) {
                 lane2.reset(new (std::nothrow) LaneGuard(ctx->dev, true));
@@ -780,8 +775,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                     L.d_pass = d_pass; L.n_refs = n; L.n_bq = (uint32_t)bqs.size();
                     uint32_t pm = 1; for (const BatchQ& e : bqs) pm = std::max(pm, e.rank_hi - e.rank_lo);
                     L.p_cap = round_slice ? (pm + 15u) & ~15u : (pm + 63u) & ~63u;      // (the slice join's LDS arrays are indexed by pair alone: no need for whole waves of them)
-                    const bool one_off = sw.gsi_onepass.get() && sw.gsi_onepass.get()[0] == '0';      // tests, A/B: count pass + scan + emit pass
-                    L.gsi_onepass = !one_off && !round_slice;
+                    L.gsi_onepass = !sw.gsi_onepass.off() && !round_slice;      // (PSK_GSI_ONEPASS=0, tests: count pass + scan + emit pass)
                     if (round_slice && lrc == PSK_OK) {      // wave table + per-(pair, slice) records of the batch
                         gsl_qn.resize(bqs.size());
                         for (size_t e = 0; e < bqs.size(); e++) gsl_qn[e] = h_qd[bqs[e].q].n;

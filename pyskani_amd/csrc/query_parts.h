@@ -10,26 +10,24 @@ static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---- the test / A-B switches of the query path ($PSK_*; profiles/r6/paths.md maps each to the test that covers it). A call (psk_query*, psk_chain*, psk_screen) reads
 // them ONCE, when it begins, into this struct and hands it down: every decision of the call sees one consistent set, a test (or bench.py: PSK_PIPELINE) may flip them
-// between two calls of one process, and no kernel-launching code touches the environment. A value is kept as the text the environment held (get(): nullptr = not set).
+// between two calls of one process, and no kernel-launching code touches the environment. A value is kept as the text the environment held (get(): nullptr = not set)
+// and read as EnvVal (common.h) reads the environment.
 struct SwitchVal {
     char text[24]; bool set;
     const char* get() const { return set ? text : nullptr; }
+    bool off() const { return EnvVal{get()}.off(); }
+    int force() const { return EnvVal{get()}.force(); }
+    double num(double dflt) const { return EnvVal{get()}.num(dflt); }
 };
 #define PSK_SWITCHES(X) \
     X(chain_serial, "PSK_CHAIN_SERIAL") \
     X(join_pairs, "PSK_JOIN_PAIRS") \
-    X(gsl_stage, "PSK_GSL_STAGE") \
-    X(probe_local, "PSK_PROBE_LOCAL") \
     X(emit_pairs, "PSK_EMIT_PAIRS") \
     X(xcd_group, "PSK_XCD_GROUP") \
-    X(dp_prune, "PSK_DP_PRUNE") \
     X(chunk_hops, "PSK_CHUNK_HOPS") \
     X(emit_heads, "PSK_EMIT_HEADS") \
     X(hops_items, "PSK_HOPS_ITEMS") \
-    X(hops_unsliced, "PSK_HOPS_UNSLICED") \
-    X(gsi_stage, "PSK_GSI_STAGE") \
     X(emit_expand, "PSK_EMIT_EXPAND") \
-    X(row_sort, "PSK_ROW_SORT") \
     X(chain_lane, "PSK_CHAIN_LANE") \
     X(lane_xtrees, "PSK_LANE_XTREES") \
     X(chain_quad_deep, "PSK_CHAIN_QUAD_DEEP") \

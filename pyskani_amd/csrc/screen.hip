@@ -331,7 +331,7 @@ psk_status screen_many_device(Lane* ctx, psk_db* db, const psk_sketch* const* qu
                 PSK_HIP(hipFuncSetAttribute((const void*)inv_screen_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * INV_LDS_REFS)));
                 lds_attr = true;
             }
-            const bool wave_off = sw.screen_wave.get() && sw.screen_wave.get()[0] == '0';      // "0": one lane per marker, binary search over the whole index (A/B, tests)
+            const bool wave_off = sw.screen_wave.off();      // "0": one lane per marker, binary search over the whole index (A/B, tests)
             if (!wave_off && db->inv_n)
                 hipLaunchKernelGGL(inv_screen_wave_kernel, dim3(m), dim3(512), 4 * (size_t)n, st, (const MarkerSet*)db->d_marker_ptr.p, d_q,
                                    (const uint64_t*)db->inv_key.p, (const uint32_t*)db->inv_ref.p, (const uint32_t*)db->inv_bucket.p, 2 * K_MARKER - db->inv_bits, n, thresh, rescue_small, pass_b);

@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256) void gsi_bucket_kernel(const uint32_t* __restr
 // called with the database locked exclusively; leaves gsi_state 1 (built) or 2 (this database cannot have one)
 psk_status build_gsi(Lane* ctx, psk_db* db) {
     if (db->gsi_state) return PSK_OK;
-    static const bool off = getenv("PSK_GSI") && getenv("PSK_GSI")[0] == '0';
+    static const bool off = env_val("PSK_GSI").off();
     hipStream_t st = ctx->stream;
     const uint32_t n = (uint32_t)db->refs.size();
     db->gsi_state = 2;
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void bsi_bucket_kernel(const uint32_t* __restr
 // called with the database locked exclusively; leaves bsi_state 1 (built) or 2 (this database cannot have one)
 psk_status build_bsi(Lane* ctx, psk_db* db) {
     if (db->bsi_state) return PSK_OK;
-    static const bool off = getenv("PSK_GSI") && getenv("PSK_GSI")[0] == '0';
+    static const bool off = env_val("PSK_GSI").off();
     hipStream_t st = ctx->stream;
     const uint32_t n = (uint32_t)db->refs.size();
     db->bsi_state = 2;

@@ -623,10 +623,10 @@ psk_status small_query_sketch_enqueue(Lane* ctx, const psk_params* p, const Smal
 }
 struct ToU64 { __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; } };
 
-// One sub-batch of genomes moving through the sketch pipeline on its own stream. The phases are split
+// A batch of genomes moving through the sketch pipeline on the lane's stream. The phases are split
 // at the two points where the host must learn a size (total seeds, total distinct markers).
 struct SketchJob {
-    Lane* ctx; Lane::JobRes* R; hipStream_t st;
+    Lane* ctx; Lane::SketchRes* R; hipStream_t st;
     const psk_params* p; const uint8_t* d_bases; int want_seeds;
     const uint32_t* packed_in = nullptr;      // the bases arrive 2-bit packed, tile by tile in this job's tile order (host ingest): d_bases is not read
     uint32_t n_genomes = 0, n_tiles = 0; int n_desc = 0;
@@ -695,7 +695,7 @@ struct SketchJob {
     }
 
     // tables up, pack + seed bits, tile offsets, per-genome / per-contig seed offsets on their way back
-    psk_status phase1(hipEvent_t wait_scan) {
+    psk_status phase1() {
         if (empty) return PSK_OK;
         size_t o_cnt = 0, o_toff = o_cnt + n_tiles + 1, o_gft = o_toff + n_tiles + 1, o_cft = o_gft + n_genomes + 1,
                o_goff = o_cft + n_desc + 1, o_coff = o_goff + n_genomes + 1, o_mcnt = o_coff + n_desc + 1,
@@ -736,15 +736,10 @@ struct SketchJob {
         JHIP(hipMemsetAsync(d_tmc + n_tiles, 0, sizeof(uint32_t), st));
         JHIP(hipMemsetAsync(d_moff + n_genomes, 0, sizeof(uint32_t), st));
         hipLaunchKernelGGL(tile_contig_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, st, d_desc, n_desc, n_tiles, d_tci, d_tinfo);
-        if (wait_scan) JHIP(hipStreamWaitEvent(st, wait_scan, 0));   // scans run one after another; emit/sorts fill in beside them
         ctx->t_begin(K_SKETCH_SCAN, st);
-        // optional dynamic-LDS ballast caps the scan's residency so that the latency-bound emit/sort kernels of the
-        // previous sub-batch find free wave slots beside it (the scan is issue-bound well below 8 waves/SIMD)
-        static const int scan_lds = getenv("PSK_SCAN_LDS") ? atoi(getenv("PSK_SCAN_LDS")) : 0;
-        if (packed_in) hipLaunchKernelGGL(sketch_scan_packed_kernel, dim3(n_tiles), dim3(TILE_THREADS), scan_lds, st, d_desc, d_tci, d_packed, d_mask, d_cnt, C);
-        else hipLaunchKernelGGL(sketch_scan_kernel, dim3(n_tiles), dim3(TILE_THREADS), scan_lds, st, d_bases, d_desc, d_tci, d_packed, d_mask, d_cnt, C);
+        if (packed_in) hipLaunchKernelGGL(sketch_scan_packed_kernel, dim3(n_tiles), dim3(TILE_THREADS), 0, st, d_desc, d_tci, d_packed, d_mask, d_cnt, C);
+        else hipLaunchKernelGGL(sketch_scan_kernel, dim3(n_tiles), dim3(TILE_THREADS), 0, st, d_bases, d_desc, d_tci, d_packed, d_mask, d_cnt, C);
         ctx->t_end(st);
-        JHIP(hipEventRecord(R->scan_done, st));
         size_t tmp_bytes = 0;
         JHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_cnt, d_toff, (int)(n_tiles + 1), st));
         PSK_TRY(R->s_tmp.reserve(tmp_bytes));
@@ -821,7 +816,7 @@ struct SketchJob {
         // Few genomes with millions of markers each (Gb-scale): a segmented sort hands each segment to too few workgroups (60 ms for
         // 8 x 3 M markers); tagged with the genome number, one device-wide radix sort does all of them (PSK_MARKER_TAGSORT=0: segmented)
         int gbits = 0; while ((1ull << gbits) < (uint64_t)n_genomes + 1) gbits++;      // tags 0 .. n_genomes - 1, and n_genomes for the padding
-        static const bool tag_off = getenv("PSK_MARKER_TAGSORT") && getenv("PSK_MARKER_TAGSORT")[0] == '0';
+        static const bool tag_off = env_val("PSK_MARKER_TAGSORT").off();
         const bool tagged = !tag_off && MARKER_BITS + gbits <= 64;
         if (!marker_dense_ready) hipLaunchKernelGGL(marker_compact_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, st, d_mstage, d_toff, d_tmoff, n_tiles, d_mdense, tagged ? (const uint4*)d_tinfo : (const uint4*)nullptr);
         marker_dense_ready = true;      // (the sorts below leave their input as it is)
@@ -849,8 +844,8 @@ struct SketchJob {
         uint64_t est = 0;
         for (uint32_t g = 0; g < n_genomes; g++) est = std::max<uint64_t>(est, g_total_len[g] / (uint64_t)p->marker_c);
         marker_slices = (uint32_t)std::min<uint64_t>(512, std::max<uint64_t>(1, est / 8192));
-        if (const char* e = getenv("PSK_MARKER_SLICES")) marker_slices = (uint32_t)std::max(1, std::min(1024, atoi(e)));      // tests: slices whatever the size
-        if (marker_slices > 1 && (uint64_t)marker_slices * n_genomes <= (1u << 20) && !getenv("PSK_MARKER_UNSLICED")) {
+        if (const EnvVal e = env_val("PSK_MARKER_SLICES"); e.text) marker_slices = (uint32_t)std::max(1, std::min(1024, (int)e.num(0)));      // tests: slices whatever the size
+        if (marker_slices > 1 && (uint64_t)marker_slices * n_genomes <= (1u << 20)) {
             PSK_TRY(R->s_slices.reserve(4 * (size_t)marker_slices * n_genomes + 256));
             uint32_t* d_sc = (uint32_t*)R->s_slices.p;
             hipLaunchKernelGGL(marker_unique_sliced_kernel<0>, dim3(marker_slices, n_genomes), dim3(256), 0, st, d_msorted, d_mstage, d_sbeg, d_sbeg + 1, d_sc);
@@ -903,7 +898,7 @@ struct SketchJob {
     // completion). *done = false: not eligible, or a count did not fit (low-complexity input) - the general path runs instead.
     psk_status run_small(psk_sketch** out, bool* done) {
         *done = false;
-        const bool off = getenv("PSK_SKETCH_SMALL") && getenv("PSK_SKETCH_SMALL")[0] == '0';
+        const bool off = env_val("PSK_SKETCH_SMALL").off();
         if (off || empty || n_genomes != 1 || n_tiles > (uint32_t)MB_TILES || n_desc > 65536) return PSK_OK;
         const uint64_t bases = sk[0]->total_len;
         if (bases / (uint64_t)p->marker_c > (uint64_t)(MB_CAP * 3 / 4)) return PSK_OK;
@@ -1005,51 +1000,31 @@ psk_status sketch_batch_impl(Lane* ctx, const psk_params* p, const uint8_t* d_ba
     if (p->k < 1 || p->k > 16) { psk_set_error("Value of k > 16 for DNA; not allowed (k=%d)", p->k); return PSK_EINVAL; }
     if (p->c < 1 || p->marker_c < 1) { psk_set_error("compression factors must be >= 1"); return PSK_EINVAL; }
     for (uint32_t g = 0; g < n_genomes; g++) out[g] = nullptr;
-    // The pipeline can run as J sub-batches on J streams (PSK_SKETCH_JOBS), sub-batch j+1 scanning while
-    // sub-batch j emits and sorts. Measured on MI355X (profiles/r1d_overlap.md) this gains nothing: scan AND
-    // emit are both VALU-issue bound, overlapped they slow each other by exactly what they take. Default J = 1.
-    uint64_t total = 0;
-    std::vector<uint64_t> gb(n_genomes);
-    for (uint32_t g = 0; g < n_genomes; g++) {
-        uint64_t b = 0;
-        for (uint32_t c = genome_first_contig[g]; c < genome_first_contig[g + 1]; c++) b += contig_len[c];
-        gb[g] = b; total += b;
-    }
-    const char* env = getenv("PSK_SKETCH_JOBS");
-    uint32_t J = env && !d_packed_in ? (uint32_t)atoi(env) : 1u;      // (packed input is laid out in ONE job's tile order)
-    J = std::max(1u, std::min(J, std::min(8u, n_genomes ? n_genomes : 1u)));
-    std::vector<uint32_t> cut(J + 1, n_genomes);
-    cut[0] = 0;
-    { uint64_t acc = 0; uint32_t j = 1; for (uint32_t g = 0; g < n_genomes && j < J; g++) { acc += gb[g]; if (acc >= total * j / J) cut[j++] = g + 1; } }
-    std::vector<SketchJob> jobs(J);
+    // (the whole batch is one job on the lane's stream: sub-batches on streams of their own, one scanning while another emits and sorts, gained nothing -
+    // scan and emit are both VALU-issue bound, overlapped they slow each other by exactly what they take; profiles/r1d_overlap.md)
+    SketchJob jb{};
     auto abort_all = [&](psk_status rc) {
-        for (auto& jb : jobs) if (jb.R) (void)hipStreamSynchronize(jb.R->stream);
-        for (auto& jb : jobs) jb.drop();
+        (void)hipStreamSynchronize(jb.st);
+        jb.drop();
         for (uint32_t g = 0; g < n_genomes; g++) { delete out[g]; out[g] = nullptr; }
         return rc;
     };
-    for (uint32_t j = 0; j < J; j++) {
-        SketchJob& jb = jobs[j];
-        jb.ctx = ctx; jb.p = p; jb.d_bases = d_bases; jb.want_seeds = want_seeds; jb.packed_in = d_packed_in;
-        psk_status rc = ctx->job(j, &jb.R);
-        if (rc != PSK_OK) return abort_all(rc);
-        jb.st = jb.R->stream;
-        rc = jb.prepare(contig_off, contig_len, genome_first_contig + cut[j], cut[j + 1] - cut[j]);
-        if (rc != PSK_OK) return abort_all(rc);
-    }
-    if (J == 1 && n_genomes == 1 && !d_packed_in) {
+    jb.ctx = ctx; jb.R = &ctx->sk; jb.st = ctx->stream; jb.p = p; jb.d_bases = d_bases; jb.want_seeds = want_seeds; jb.packed_in = d_packed_in;
+    psk_status rc = jb.prepare(contig_off, contig_len, genome_first_contig, n_genomes);
+    if (rc != PSK_OK) return abort_all(rc);
+    if (n_genomes == 1 && !d_packed_in) {
         bool done = false;
-        jobs[0].make_objects();
-        psk_status rc = jobs[0].run_small(out, &done);
+        jb.make_objects();
+        rc = jb.run_small(out, &done);
         if (rc != PSK_OK) return abort_all(rc);
         if (done) return PSK_OK;
     }
-    hipEvent_t prev = nullptr;
-    for (uint32_t j = 0; j < J; j++) { psk_status rc = jobs[j].phase1(prev); if (rc != PSK_OK) return abort_all(rc); if (!jobs[j].empty) prev = jobs[j].R->scan_done; }
-    for (uint32_t j = 0; j < J; j++) jobs[j].make_objects();      // (while the scans run)
-    for (uint32_t j = 0; j < J; j++) { psk_status rc = jobs[j].phase2(); if (rc != PSK_OK) return abort_all(rc); }
-    for (uint32_t j = 0; j < J; j++) { psk_status rc = jobs[j].phase3(); if (rc != PSK_OK) return abort_all(rc); }
-    for (uint32_t j = 0; j < J; j++) { psk_status rc = jobs[j].finish(out + cut[j]); if (rc != PSK_OK) return abort_all(rc); }
+    rc = jb.phase1();
+    if (rc != PSK_OK) return abort_all(rc);
+    jb.make_objects();      // (while the scan runs)
+    rc = jb.phase2(); if (rc != PSK_OK) return abort_all(rc);
+    rc = jb.phase3(); if (rc != PSK_OK) return abort_all(rc);
+    rc = jb.finish(out); if (rc != PSK_OK) return abort_all(rc);
     return PSK_OK;
 }
 
@@ -1289,7 +1264,7 @@ psk_status ensure_index(Lane* ctx, const psk_sketch* const* refs, uint32_t n, bo
             // 101 sketches: 8 slices are no faster than 1 (0.38 vs 0.33 ms for the whole marker + index phase) - the
             // kernel's time is its chain of dependent round trips, not one CU's scattered traffic. PSK_INDEX_SLICES overrides.
             uint32_t slices = 1;
-            if (const char* e = getenv("PSK_INDEX_SLICES")) slices = (uint32_t)std::max(1, std::min(8, atoi(e)));
+            if (const EnvVal e = env_val("PSK_INDEX_SLICES"); e.text) slices = (uint32_t)std::max(1, std::min(8, (int)e.num(0)));
             if (tiny) hipLaunchKernelGGL((index_block_kernel<256, IDXT_MAX_LB>), dim3(m), dim3(256), 0, st, d_segs, segs[0], 1u, ix->key, ix->perm, ix->pms, ix->bucket, ix->km32);
             else hipLaunchKernelGGL((index_block_kernel<IDXB_THREADS, IDXB_MAX_LB>), dim3(m * slices), dim3(IDXB_THREADS), 0, st, d_segs, segs[0], slices, ix->key, ix->perm, ix->pms, ix->bucket, ix->km32);
             ctx->t_end();
@@ -1305,7 +1280,7 @@ psk_status ensure_index(Lane* ctx, const psk_sketch* const* refs, uint32_t n, bo
             i0 = i1;
             continue;
         }
-        bool own_sort = getenv("PSK_INDEX_GROUP_SORT") == nullptr;      // (tests, A/B: the group sort for sketches of any size)
+        bool own_sort = true;
         int kb_max = 0;
         for (uint32_t j = 0; j < m; j++) { own_sort = own_sort && segs[j].n >= IDX_OWN_SORT; kb_max = std::max(kb_max, 2 * todo[i0 + j]->params.k); }
         if (own_sort) {

@@ -35,7 +35,6 @@ struct GslArgs {
     const uint32_t* pstart; uint4* anc; uint32_t cap; uint32_t* err;      // err = the launch sequence's status words (bit 0: chunk table overflow, bit 1: capacity; [5]: rerun wide; [16..17]: 64-bit anchor total)
     uint32_t p_cap;      // most pairs any entry of the batch holds, rounded up to 64
     uint2* chunks; uint32_t* n_chunks;
-    int stage;           // emit walk: 1 = a pair's anchors leave as whole 64-byte lines staged in LDS, 0 = every anchor its own 16-byte store (A/B)
 };
 
 // wave table of a batch: (entry, slice) for every slice of every entry's query, a query's slices one after the other; ebase: per entry (first record, first slice)

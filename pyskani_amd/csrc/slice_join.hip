@@ -59,7 +59,7 @@ static size_t gsl_walk_lds(const GslArgs& A, bool emit) {
 
 // (streaming - nontemporal - stores of the anchors were measured on the 10 000 x 10 000 step: the walk takes the same time and the DP kernel that reads the anchors next 178 instead of
 // 165 ms: plain stores; profiles/r5/r5_ablation.md)
-template <bool EMIT, bool STAGE>
+template <bool EMIT>
 __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
     extern __shared__ uint4 s_gsl[];
     const int lane = threadIdx.x;
@@ -205,7 +205,6 @@ __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
                 }
                 if (!dup) {      // every valid lane has a pair of its own (a reference holds a k-mer once, nearly always): nothing to order between lanes
                     // (no capacity test on this path: the count walk's total was held against the capacity before this kernel started - see the guard at its top)
-                    if (!STAGE) { if (valid) { s_cs[slot].x = base + 1u; A.anc[base] = av; } continue; }
                     const uint32_t t3 = base & GSL_LM;
                     if (valid) { s_cs[slot].x = base + 1u; s_line[t3 * pc + slot] = av; }
                     // complete lines leave TOGETHER: four consecutive lanes write one pair's 64 bytes (one request per line where a lane writing its own line makes four)
@@ -235,13 +234,6 @@ __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
                 const unsigned long long ends = __ballot(last);
                 const uint32_t tail = valid ? (uint32_t)__ffsll((long long)(ends >> lane)) - 1u : 0u;      // lanes of the group after this one
                 const uint32_t d = base + jj, e = d + tail, lastline = e >> GSL_LS;
-                if (!STAGE) {
-                    if (valid) { if (d < A.cap) A.anc[d] = av; else atomicOr(A.err, 2u); }
-                    lds_wave_sync();
-                    if (last) s_cs[slot].x = e + 1u;
-                    lds_wave_sync();
-                    continue;
-                }
                 // (A) a group that runs past the line being staged: its first lane sends out what the line holds so far
                 if (valid && jj == 0 && (base >> GSL_LS) != lastline && e < A.cap) {
                     const uint32_t f0 = (base & ~GSL_LM) > st0 ? (base & ~GSL_LM) : st0;
@@ -281,7 +273,7 @@ __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
             if (c) atomicAdd(&A.pair_cnt[B.pair_off + j], c);
         }
         for (uint32_t x = lane; x < P * GSL_WORDS; x += 64) { const uint32_t j = x / GSL_WORDS, w = x % GSL_WORDS; A.bm[(size_t)(rec0 + j) * GSL_WORDS + w] = s_bm[w * (pc + 1u) + j]; }
-    } else if (STAGE) {
+    } else {
         for (uint32_t j = lane; j < P; j += 64) {      // what is left in the lines: the pairs' last anchors of the slice
             const uint32_t c = s_cs[j].x, st0 = s_cs[j].y;
             if (c > st0 && (c & GSL_LM) && c <= A.cap) {
@@ -430,7 +422,7 @@ psk_status gsl_blocks_launch(const BatchQ* bq, uint32_t n_entries, const uint8_t
     return PSK_OK;
 }
 psk_status gsl_count_launch(const GslArgs& A, hipStream_t st) {
-    hipLaunchKernelGGL((gsl_walk_kernel<false, false>), dim3(A.n_tab), dim3(64), gsl_walk_lds(A, false), st, A);
+    hipLaunchKernelGGL(gsl_walk_kernel<false>, dim3(A.n_tab), dim3(64), gsl_walk_lds(A, false), st, A);
     PSK_HIP(hipGetLastError());
     return PSK_OK;
 }
@@ -441,8 +433,7 @@ psk_status gsl_heads_launch(const GslArgs& A, hipStream_t st) {
     return PSK_OK;
 }
 psk_status gsl_emit_launch(const GslArgs& A, hipStream_t st) {
-    if (A.stage) hipLaunchKernelGGL((gsl_walk_kernel<true, true>), dim3(A.n_tab), dim3(64), gsl_walk_lds(A, true), st, A);
-    else hipLaunchKernelGGL((gsl_walk_kernel<true, false>), dim3(A.n_tab), dim3(64), gsl_walk_lds(A, true), st, A);
+    hipLaunchKernelGGL(gsl_walk_kernel<true>, dim3(A.n_tab), dim3(64), gsl_walk_lds(A, true), st, A);
     PSK_HIP(hipGetLastError());
     return PSK_OK;
 }

@@ -659,7 +659,7 @@ inline size_t al256q(size_t x) { return (x + 255) & ~(size_t)255; }
 psk_status query_host_small(Lane* ctx, psk_db* db, const uint8_t* const* contigs, const uint64_t* lens, uint32_t n_contigs, const psk_query_opts* o,
                             HitList& all, bool* done) {
     *done = false;
-    static const bool off = getenv("PSK_SMALL_QUERY") && getenv("PSK_SMALL_QUERY")[0] == '0';
+    static const bool off = env_val("PSK_SMALL_QUERY").off();
     if (off) return PSK_OK;
     const psk_params prm = db->params;
     if (prm.k < 1 || prm.k > 16 || prm.c < 1 || prm.marker_c < 1) return PSK_OK;
@@ -721,7 +721,7 @@ psk_status query_host_small(Lane* ctx, psk_db* db, const uint8_t* const* contigs
     }
     // PSK_SQ_ZEROCOPY=0: the input crosses with an upload command and the results with a download command (A/B); default: the kernels read the pinned
     // input block in place (a contig is tens of kilobytes) and the chain kernel's last workgroup writes the results into pinned memory - two commands fewer in the stream
-    static const bool zc = !(getenv("PSK_SQ_ZEROCOPY") && getenv("PSK_SQ_ZEROCOPY")[0] == '0');
+    static const bool zc = !env_val("PSK_SQ_ZEROCOPY").off();
     char* In = zc ? Hin : D;
     if (!zc) PSK_HIP(hipMemcpyAsync(D, Hin, in_bytes, hipMemcpyHostToDevice, st));
     SmallQHead* d_head = (SmallQHead*)(D + w_out);
@@ -740,7 +740,7 @@ psk_status query_host_small(Lane* ctx, psk_db* db, const uint8_t* const* contigs
     SA.thresh = pow(o->cutoff != 0.0 ? o->cutoff : 0.80, (double)K_MARKER); SA.rescue_small = !o->faster_small;      // lib.rs:597, 603-609
     SA.canon = db->has_dups ? (const uint32_t*)db->d_canon.p : nullptr;
     SA.shortlist = (uint32_t*)(D + w_short);
-    static const bool pf_off = getenv("PSK_SQ_PREFILTER") && getenv("PSK_SQ_PREFILTER")[0] == '0';      // tests, A/B
+    static const bool pf_off = env_val("PSK_SQ_PREFILTER").off();      // tests, A/B
     if (db->gsi_state == 1 && !pf_off) { SA.gsi_key = (const uint32_t*)db->gsi_key.p; SA.gsi_val = (const unsigned long long*)db->gsi_val.p; SA.gsi_bucket = (const uint32_t*)db->gsi_bucket.p; SA.gsi_shift = db->gsi_shift; }
     SA.q_kmer = S.seed_kmer;
     static std::once_flag lds_once;
@@ -763,14 +763,14 @@ psk_status query_host_small(Lane* ctx, psk_db* db, const uint8_t* const* contigs
     const size_t prof_off = (offsetof(SmallQHead, pad1) + 7) & ~(size_t)7;      // (seven 8-byte words inside the status block's padding)
     CA.prof = prof_on ? (unsigned long long*)((char*)d_head + prof_off) : nullptr;
     CA.host_out = zc ? (uint4*)Hout : nullptr;
-    static const bool no_team = getenv("PSK_SQ_TEAM") && getenv("PSK_SQ_TEAM")[0] == '0';
+    static const bool no_team = env_val("PSK_SQ_TEAM").off();
     CA.no_team = no_team;
     ctx->t_begin(K_CHAIN_CHUNK);
     // The shortlist's length is known on the device only, and a workgroup of this kernel holds 77 KB of LDS: a grid sized for the worst case (every
     // reference) is a thousand workgroups that queue for LDS only to find nothing to do - from eight host threads they held the rate at 20 k queries/s
     // where 128-256 workgroups give 31 k (profiles/r4/r4i_grid.txt). The grid follows the LAST call's shortlist on this lane (neighbouring queries of a
     // workload have similar shortlists); a longer one is walked in several rounds by the same workgroups. PSK_SQ_GRID fixes it (A/B).
-    static const uint32_t grid_env = getenv("PSK_SQ_GRID") ? (uint32_t)std::max(1, atoi(getenv("PSK_SQ_GRID"))) : 0u;
+    static const uint32_t grid_env = [] { const EnvVal e = env_val("PSK_SQ_GRID"); return e.text ? (uint32_t)std::max(1, (int)e.num(0)) : 0u; }();
     const uint32_t grid = grid_env ? grid_env : std::max(64u, std::min(1024u, ctx->sq_last_short + ctx->sq_last_short / 4 + 16u));
     hipLaunchKernelGGL(sq_chain_kernel, dim3(std::min<uint32_t>(n_refs, grid)), dim3(SQ_CHAIN_T), 0, st, CA);
     PSK_HIP(hipGetLastError());

@@ -66,16 +66,13 @@ def test_random_pairs_match_oracle(psk, oracle, seed, monkeypatch):
                 monkeypatch.setenv("PSK_GSI_JOIN", "0")
             elif seed % 32 == 9:
                 monkeypatch.setenv("PSK_GSI_ONEPASS", "0")      # ... the index join with its count pass (without: anchors placed at the pairs' item offsets, one walk)
-            elif seed % 32 == 25:
-                monkeypatch.setenv("PSK_GSI_STAGE", "0")        # ... every anchor its own 16-byte store (default: an even-indexed anchor waits in LDS for its neighbour)
     if seed % 4 == 2:
         monkeypatch.setenv("PSK_EMIT_PAIRS", "1")   # ... and the one-workgroup-per-pair emit (join's pair totals) another,
         monkeypatch.setenv("PSK_CHUNK_HOPS", "0")   # chunk table included
         monkeypatch.setenv("PSK_SKETCH_SMALL", "0") # ... behind the count-then-allocate sketch pipeline (a single genome takes the one-synchronisation path otherwise)
         if seed % 8 == 6:
             monkeypatch.setenv("PSK_GSI_SLICE", "1")    # ... or (every other time) the seed-index join by (query, slice) waves - the all-vs-all default - forced on one pair:
-            if seed % 16 == 14:                         # repeats (several anchors per seed and pair), strands, contigs, slices of 512 seeds; staged whole-line stores or plain ones
-                monkeypatch.setenv("PSK_GSL_STAGE", "0")
+                                                        # repeats (several anchors per seed and pair), strands, contigs, slices of 512 seeds
     for _ in range(4):
         k, c, mc, ref, qry = _case(rng)
         kw = {"median": True} if rng.random() < 0.2 else ({"robust": True} if rng.random() < 0.2 else {})

@@ -322,9 +322,9 @@ def test_alternative_device_paths_agree(ecoli):
     ) % (ROOT, os.path.join(ROOT, "tests"))
     outs = {}
     for name, extra in (("default", {}), ("wave_dp", {"PSK_CHAIN_LANE": "0"}), ("lane_dp", {"PSK_CHAIN_LANE": "64"}), ("quad_dp", {"PSK_CHAIN_LANE": "q"}), ("hops", {"PSK_CHUNK_HOPS": "1"}), ("hops_over_items", {"PSK_CHUNK_HOPS": "1", "PSK_HOPS_ITEMS": "1"}), ("hops_over_items_wide", {"PSK_CHUNK_HOPS": "1", "PSK_HOPS_ITEMS": "1", "PSK_JOIN": "wide"}), ("walk", {"PSK_CHUNK_HOPS": "0"}), ("serial", {"PSK_CHAIN_SERIAL": "1"}), ("radix_index", {"PSK_INDEX_RADIX": "1"}), ("wide_join", {"PSK_JOIN": "wide"}), ("pair_join", {"PSK_JOIN_PAIRS": "1"}), ("emit_per_pair", {"PSK_EMIT_PAIRS": "1"}), ("emit_per_pair_with_chunk_table", {"PSK_EMIT_PAIRS": "1", "PSK_CHUNK_HOPS": "0"}),
-                        ("reduce_by_workgroup", {"PSK_REDUCE_WAVE": "0"}), ("reduce_by_workgroup_only", {"PSK_REDUCE_SMALL": "0"}), ("rows_in_table_order", {"PSK_ROW_SORT": "0"})):      # (the pair's ~230 chunk rows: reduced by one wave, four rows per lane, by default)
+                        ("reduce_by_workgroup", {"PSK_REDUCE_WAVE": "0"}), ("reduce_by_workgroup_only", {"PSK_REDUCE_SMALL": "0"})):      # (the pair's ~230 chunk rows: reduced by one wave, four rows per lane, by default)
         env = dict(os.environ)
-        for k in ("PSK_HOPS_ITEMS", "PSK_CHAIN_SERIAL", "PSK_CHAIN_LANE", "PSK_CHUNK_HOPS", "PSK_INDEX_RADIX", "PSK_JOIN", "PSK_JOIN_PAIRS", "PSK_EMIT_PAIRS", "PSK_REDUCE_WAVE", "PSK_REDUCE_SMALL", "PSK_ROW_SORT"):
+        for k in ("PSK_HOPS_ITEMS", "PSK_CHAIN_SERIAL", "PSK_CHAIN_LANE", "PSK_CHUNK_HOPS", "PSK_INDEX_RADIX", "PSK_JOIN", "PSK_JOIN_PAIRS", "PSK_EMIT_PAIRS", "PSK_REDUCE_WAVE", "PSK_REDUCE_SMALL"):
             env.pop(k, None)
         env.update(extra)
         outs[name] = subprocess.check_output([sys.executable, "-c", code], env=env, timeout=600).decode().strip()

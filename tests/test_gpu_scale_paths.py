@@ -56,7 +56,7 @@ print(*digest(db.query_many(contigs, learned_ani=False)))
 
 def _run(code, extra):
     env = dict(os.environ)
-    for k in ("PSK_EMIT_PAIRS", "PSK_EMIT_HEADS", "PSK_XCD_GROUP", "PSK_BATCH_ITEMS_LOG2", "PSK_PREFILTER", "PSK_JOIN_PAIRS", "PSK_CHUNK_HOPS", "PSK_PROBE", "PSK_CHAIN_QUAD_DEEP", "PSK_SELECT_TINY", "PSK_CHAIN_WAVE_REG", "PSK_ROW_SORT", "PSK_ROUND_QUERIES", "PSK_REDUCE_TINY", "PSK_PROBE_LOCAL", "PSK_REDUCE_SMALL", "PSK_GSI_JOIN", "PSK_GSI_ONEPASS", "PSK_DP_PRUNE", "PSK_GSI_SLICE", "PSK_GSL_STAGE", "PSK_GSL_MAX_BLOCKS", "PSK_BSI_SMALL", "PSK_GSI_STAGE", "PSK_PIPELINE", "PSK_BIG_SOLO", "PSK_HUGE_MIN_SEEDS", "PSK_HUGE_SLOTS"):
+    for k in ("PSK_EMIT_PAIRS", "PSK_EMIT_HEADS", "PSK_XCD_GROUP", "PSK_BATCH_ITEMS_LOG2", "PSK_PREFILTER", "PSK_JOIN_PAIRS", "PSK_CHUNK_HOPS", "PSK_PROBE", "PSK_CHAIN_QUAD_DEEP", "PSK_SELECT_TINY", "PSK_CHAIN_WAVE_REG", "PSK_ROUND_QUERIES", "PSK_REDUCE_TINY", "PSK_REDUCE_SMALL", "PSK_GSI_JOIN", "PSK_GSI_ONEPASS", "PSK_GSI_SLICE", "PSK_GSL_MAX_BLOCKS", "PSK_BSI_SMALL", "PSK_PIPELINE", "PSK_BIG_SOLO", "PSK_HUGE_MIN_SEEDS", "PSK_HUGE_SLOTS"):
         env.pop(k, None)
     env.update(extra)
     out = subprocess.check_output([sys.executable, "-c", code], env=env, timeout=900).decode().split()
@@ -70,8 +70,8 @@ def test_all_vs_all_batch_paths_agree():
     # (the default joins such a batch through the database-wide seed index, one wave per (query, slice of 512 seeds): slice_join.hip; PSK_GSI_SLICE=0 = the per-pair
     # merge join + per-pair emit it replaced, which stays the route of databases that cannot have the index - its switches only act there)
     # (PSK_PIPELINE=1: alternate batches on a second lane, two in flight - the default of rounds of >= 2^31 (pair, seed) items - here over nine batches, and over one)
-    for extra in ({"PSK_GSI_SLICE": "0"}, {"PSK_GSL_STAGE": "0", "PSK_BATCH_ITEMS_LOG2": "22"}, {"PSK_PIPELINE": "1", "PSK_BATCH_ITEMS_LOG2": "22"}, {"PSK_PIPELINE": "1"}, {"PSK_PIPELINE": "0", "PSK_BATCH_ITEMS_LOG2": "23"}, {"PSK_GSI_SLICE": "0", "PSK_EMIT_PAIRS": "0"}, {"PSK_GSI_SLICE": "0", "PSK_EMIT_HEADS": "0", "PSK_XCD_GROUP": "0"},
-                  {"PSK_GSI_SLICE": "0", "PSK_BATCH_ITEMS_LOG2": "22", "PSK_ROW_SORT": "0"}, {"PSK_GSI_SLICE": "0", "PSK_CHUNK_HOPS": "1", "PSK_REDUCE_SMALL": "0"}):
+    for extra in ({"PSK_GSI_SLICE": "0"}, {"PSK_BATCH_ITEMS_LOG2": "22"}, {"PSK_PIPELINE": "1", "PSK_BATCH_ITEMS_LOG2": "22"}, {"PSK_PIPELINE": "1"}, {"PSK_PIPELINE": "0", "PSK_BATCH_ITEMS_LOG2": "23"}, {"PSK_GSI_SLICE": "0", "PSK_EMIT_PAIRS": "0"}, {"PSK_GSI_SLICE": "0", "PSK_EMIT_HEADS": "0", "PSK_XCD_GROUP": "0"},
+                  {"PSK_GSI_SLICE": "0", "PSK_BATCH_ITEMS_LOG2": "22"}, {"PSK_GSI_SLICE": "0", "PSK_CHUNK_HOPS": "1", "PSK_REDUCE_SMALL": "0"}):
         assert _run(ALL_VS_ALL, extra) == base, extra
 
 
@@ -216,7 +216,6 @@ def test_slice_join_with_more_pairs_than_one_entry_holds(oracle):
     base = _run(ONE_FAMILY, {})
     assert base[0] > 80000      # (the far ends of the family - 12 % apart - fall below the screen or the aligned fraction)
     assert _run(ONE_FAMILY, {"PSK_GSI_SLICE": "0"}) == base
-    assert _run(ONE_FAMILY, {"PSK_GSL_STAGE": "0"}) == base
     assert _run(ONE_FAMILY, {"PSK_PIPELINE": "1", "PSK_BATCH_ITEMS_LOG2": "21"}) == base      # two batches in flight, entries of one query in different batches
     import numpy as np
     import pyskani_amd as psk
@@ -256,14 +255,13 @@ def test_rescue_prefilter_agrees_at_scale():
     # (the default joins these many small pairs through the references' probe tables, hands the DP its rows by chunk length, selects and reduces the
     # pairs of a handful of rows by one lane each, takes the anchor offsets from the join's running counts; switches of different stages share a run)
     for extra in ({"PSK_PREFILTER": "0"},
-                  {"PSK_GSI_ONEPASS": "0", "PSK_DP_PRUNE": "0"},                                              # the index join with its count pass; every DP scoring its whole band
-                  {"PSK_GSI_STAGE": "0"},                                                                   # every anchor of the index join its own 16-byte store (default: pairs of 32 bytes)
+                  {"PSK_GSI_ONEPASS": "0"},                                                                 # the index join with its count pass
                   {"PSK_BSI_SMALL": "0"},                                                                   # the database-wide seed index in one walk instead of its blocks of 256 references
                   {"PSK_GSI_JOIN": "0"},                                                                    # the probe-table join instead of the database-wide seed index
                   {"PSK_GSI_JOIN": "0", "PSK_PREFILTER": "0"},
                   {"PSK_PREFILTER": "1", "PSK_JOIN_PAIRS": "0"},
                   {"PSK_PROBE": "0", "PSK_PREFILTER": "0", "PSK_SELECT_TINY": "0", "PSK_REDUCE_TINY": "0"},      # joins through the k-mer indexes, a wave per pair in selection and reduce
-                  {"PSK_ROW_SORT": "0", "PSK_PROBE_LOCAL": "0", "PSK_ROUND_QUERIES": "700"},                  # rows in table order, offsets by a scan over the items, seven rounds of queries
+                  {"PSK_ROUND_QUERIES": "700"},                                                             # seven rounds of queries
                   {"PSK_CHAIN_WAVE_REG": "1", "PSK_PREFILTER": "1"},                                        # the small launch's register-window DP forced on the large batch
                   {"PSK_CHAIN_QUAD_DEEP": "0", "PSK_SELECT_TINY": "0"}):                                     # c = 30 (band 83): the wave-per-chunk LDS-ring DP
         assert _run(RESCUE, extra) == base, extra
@@ -423,7 +421,7 @@ def test_index_blocks_beyond_the_first_sixty_four(oracle, tmp_path):
     n_hits, dig, lookups = int(out[0]), out[1], int(out[2])
     assert n_hits > 500 * 40 and lookups > 0, out      # (the index joins count their lookups; the joins without an index leave the counter alone)
     env.pop("PSK_TEST_SAMPLE")
-    for extra in ({"PSK_GSI_SLICE": "0", "PSK_GSI_JOIN": "0"}, {"PSK_BSI_SMALL": "0", "PSK_GSL_STAGE": "0"}):
+    for extra in ({"PSK_GSI_SLICE": "0", "PSK_GSI_JOIN": "0"}, {"PSK_BSI_SMALL": "0"}):
         o2 = subprocess.check_output([sys.executable, "-c", MANY_BLOCKS], env=dict(env, **extra), timeout=1500).decode().split()
         assert (int(o2[0]), o2[1]) == (n_hits, dig), (extra, o2, out)
         if extra.get("PSK_GSI_JOIN") == "0":
