@@ -17,7 +17,7 @@ class _Sketch(C.Structure):
     _fields_ = [("c", C.c_int), ("marker_c", C.c_int), ("k", C.c_int), ("n_contigs", C.c_uint32),
                 ("contig_len", C.POINTER(C.c_uint32)), ("total_len", C.c_uint64),
                 ("n_seeds", C.c_uint64), ("seeds", C.c_void_p),
-                ("n_markers", C.c_uint64), ("markers", C.POINTER(C.c_uint64)), ("kindex", C.c_void_p)]
+                ("n_markers", C.c_uint64), ("markers", C.POINTER(C.c_uint64)), ("kindex", C.c_void_p), ("n_markers_raw", C.c_uint64)]
 
 
 class Node(C.Structure):
@@ -91,6 +91,8 @@ def lib():
                                         C.POINTER(C.c_uint32), C.POINTER(Result), C.c_uint32]
         _lib.orc_last_chunks.restype = C.c_uint32
         _lib.orc_last_chunks.argtypes = [C.POINTER(C.c_void_p)]
+        _lib.orc_last_chain_counts.restype = C.c_uint32
+        _lib.orc_last_chain_counts.argtypes = [C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
     return _lib
 
 
@@ -124,6 +126,11 @@ class Sketch:
     def markers(self):
         s = self._p.contents
         return np.ctypeslib.as_array(s.markers, shape=(s.n_markers,)).copy() if s.n_markers else np.zeros(0, np.uint64)
+
+    @property
+    def n_markers_raw(self):
+        """marker selections before de-duplication (`markers` holds the distinct ones)"""
+        return self._p.contents.n_markers_raw
 
     @property
     def total_len(self):
@@ -165,6 +172,15 @@ def last_chunks():
         return np.zeros(0, dtype=chunk_dtype)
     buf = (C.c_char * (n * chunk_dtype.itemsize)).from_address(p.value)
     return np.frombuffer(buf, dtype=chunk_dtype).copy()
+
+
+def last_chain_counts():
+    """(chain roots of every chunk in chunk order, candidate chains of the pair) of the last chain() on this thread"""
+    p = C.POINTER(C.c_uint32)()
+    nc = C.c_uint32(0)
+    n = lib().orc_last_chain_counts(C.byref(p), C.byref(nc))
+    roots = np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+    return roots, nc.value
 
 
 def query(refs, q, *, median=False, robust=False, cutoff=None, faster_small=False, learned_ani=False, model=None):

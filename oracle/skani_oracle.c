@@ -88,6 +88,7 @@ orc_sketch* orc_sketch_new(const uint8_t* const* contigs, const uint64_t* lens, 
                     o->kmer = (uint32_t)cs; o->pos = (uint32_t)i; o->contig = contig_index; o->canon = (uint32_t)canon;
                 }
                 if (h < thr_m) {
+                    s->n_markers_raw++;
                     if (s->n_markers == cap_m) { cap_m *= 2; s->markers = realloc(s->markers, sizeof(uint64_t) * cap_m); }
                     s->markers[s->n_markers++] = f < r ? f : r;
                 }
@@ -162,6 +163,9 @@ static int cmp_dbl(const void* a, const void* b) {
 static __thread orc_chunk_rec* g_recs = NULL;
 static __thread uint32_t g_nrecs = 0;
 uint32_t orc_last_chunks(const orc_chunk_rec** recs) { *recs = g_recs; return g_nrecs; }
+static __thread uint32_t* g_roots = NULL;
+static __thread uint32_t g_nroots = 0, g_ncands = 0;
+uint32_t orc_last_chain_counts(const uint32_t** roots, uint32_t* n_cands) { *roots = g_roots; *n_cands = g_ncands; return g_nroots; }
 
 /* number of query seeds on `contig` with pos in [lo, hi]; seeds are in (contig,pos) order */
 static uint32_t seeds_between(const orc_sketch* q, const uint64_t* cstart, uint32_t contig, uint32_t lo, uint32_t hi) {
@@ -215,6 +219,7 @@ int orc_chain(const orc_sketch* ref, const orc_sketch* query, const orc_query_op
     memset(out, 0, sizeof *out);
     out->ani = -1.0f;
     free(g_recs); g_recs = NULL; g_nrecs = 0;
+    free(g_roots); g_roots = NULL; g_nroots = 0; g_ncands = 0;
     if (o->learned_ani == 1 && !o->model) return -2;  /* GBDT weights live inside the absent crate: a model must be supplied */
     const int k = ref->k, c = ref->c;
     uint64_t nq = query->n_seeds, nr = ref->n_seeds;
@@ -253,6 +258,7 @@ int orc_chain(const orc_sketch* ref, const orc_sketch* query, const orc_query_op
     /* pass 1: per chunk, banded chaining DP and one candidate chain per DP tree */
     uint32_t nc = 0, n_chunks_all = 0;
     uint64_t chunk_cap = 256; uint32_t* chunk_qc = malloc(sizeof(uint32_t) * chunk_cap);
+    g_roots = malloc(sizeof(uint32_t) * chunk_cap);
     uint64_t s = 0;
     while (s < na) {
         /* chunk = run of anchors on one query contig within FRAGMENT_LENGTH of the chunk's first anchor */
@@ -276,7 +282,8 @@ int orc_chain(const orc_sketch* ref, const orc_sketch* query, const orc_query_op
             else { root[x] = root[bp]; depth[x] = depth[bp] + 1; }
         }
         /* the tree's best-scoring anchor (lowest index on ties), backtracked to the root */
-        for (uint64_t x = s; x < e; x++) best[x] = UINT32_MAX;
+        uint32_t n_roots = 0;
+        for (uint64_t x = s; x < e; x++) { best[x] = UINT32_MAX; n_roots += root[x] == x; }
         for (uint64_t x = s; x < e; x++) { uint32_t rt = root[x]; if (best[rt] == UINT32_MAX || f[x] > f[best[rt]]) best[rt] = (uint32_t)x; }
         for (uint64_t x = s; x < e; x++) {
             if (root[x] != x) continue;
@@ -287,10 +294,12 @@ int orc_chain(const orc_sketch* ref, const orc_sketch* query, const orc_query_op
             cd->r0 = A[x].rp < A[b].rp ? A[x].rp : A[b].rp; cd->r1 = A[x].rp < A[b].rp ? A[b].rp : A[x].rp;
             nc++;
         }
-        if (n_chunks_all == chunk_cap) { chunk_cap *= 2; chunk_qc = realloc(chunk_qc, sizeof(uint32_t) * chunk_cap); }
-        chunk_qc[n_chunks_all++] = A[s].qc;
+        if (n_chunks_all == chunk_cap) { chunk_cap *= 2; chunk_qc = realloc(chunk_qc, sizeof(uint32_t) * chunk_cap); g_roots = realloc(g_roots, sizeof(uint32_t) * chunk_cap); }
+        chunk_qc[n_chunks_all] = A[s].qc;
+        g_roots[n_chunks_all++] = n_roots;
         s = e;
     }
+    g_nroots = n_chunks_all; g_ncands = nc;
     /* pass 2: greedy selection over ALL candidates of the pair by score: a chain is kept unless it overlaps
      * a kept chain on the query (same chunk) or on the reference (same ref contig) */
     qsort(cands, nc, sizeof(cand_t), cmp_cand);

@@ -55,6 +55,7 @@ typedef struct {
     uint64_t* markers;
     void* kindex;              /* the seeds once more, ordered by (k-mer, contig, pos): the sorted stand-in for the k-mer -> positions map a
                                 * skani Sketch carries (built with the sketch, as skani fills its map while seeding; NULL without seeds) */
+    uint64_t n_markers_raw;    /* marker selections before de-duplication (a 21-mer selected at several positions counts each time) */
 } orc_sketch;
 
 /* Learned-ANI regression model (skani::regression::get_model, lib.rs:614): gradient-boosted regression trees with
@@ -117,6 +118,10 @@ uint32_t orc_query_refs(const orc_sketch* const* refs, uint32_t n, const orc_ske
 /* debug dumps for GPU parity tests: per-chunk records of the last orc_chain call on this thread */
 typedef struct { uint32_t contig, left, right, anchors, seeds, n_intervals; } orc_chunk_rec;
 uint32_t orc_last_chunks(const orc_chunk_rec** recs);
+/* counts of the last orc_chain call on this thread: the number of chain roots (anchors with no predecessor inside the band) of
+ * EVERY chunk in chunk order, *roots pointing at them (returns the number of chunks), and in *n_cands the pair's candidate
+ * chains (trees whose best anchor has >= MIN_ANCHORS anchors and score >= MIN_SCORE2). Read-only: what capacity guards test. */
+uint32_t orc_last_chain_counts(const uint32_t** roots, uint32_t* n_cands);
 
 #ifdef __cplusplus
 }
