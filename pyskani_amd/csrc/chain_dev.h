@@ -12,6 +12,40 @@ __device__ __forceinline__ void lds_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// The slice join's 8-byte anchor (slice_join.hip emits it, the DP kernels read it): lo = q_rel | (ref contig << 1 | strand) << 16, hi = r pos, where
+// q_rel = q pos - the q pos of the head of the anchor's chunk (row_q0). A chunk spans at most FRAGMENT_LENGTH query bases and the blocked seed index the slice
+// join walks holds references of at most 2^GSI_CONTIG_BITS contigs (seed_index.hip), so no input of that join overflows it; the DP uses q only as differences
+// within one chunk. What the 16-byte record carries beside it - the q contig - is per chunk row too (row_q0).
+static_assert(FRAGMENT_LENGTH < (1u << 16), "q_rel fills the low 16 bits of a packed anchor");
+static_assert(GSI_CONTIG_BITS + 1 <= 16, "ref contig << 1 | strand fills the high 16 bits of a packed anchor");
+__device__ __forceinline__ uint2 pk_anchor(uint32_t q_rel, uint32_t r, uint32_t m) { return make_uint2((q_rel & 0xFFFFu) | (m << 16), r); }
+// (q_rel, r pos, ref contig << 1 | strand, -): one mask and one shift
+__device__ __forceinline__ uint4 pk_unpack(uint2 a) { return make_uint4(a.x & 0xFFFFu, a.y, a.x >> 16, 0u); }
+// The DP kernels read either form through this: PK = the slice join's 8-byte anchors (q relative to the row's head), else the 16-byte records
+// (q pos, r pos, ref contig << 1 | strand, q contig). Both hand out (q, r pos, ref contig << 1 | strand, -).
+template <bool PK> struct AncRd {
+    const void* a;
+    __device__ __forceinline__ uint4 operator[](size_t i) const { return PK ? pk_unpack(((const uint2*)a)[i]) : ((const uint4*)a)[i]; }
+    // anchors i .. i + 3 (i a multiple of four): W4 16-byte words, and what the words hold - loads and decoding apart, so that a caller can load ahead and
+    // keep the raw words (two registers per 8-byte anchor) until it needs the fields
+    static constexpr int W4 = PK ? 2 : 4;
+    __device__ __forceinline__ void load4w(size_t i, uint4 (&w)[W4]) const {
+        const uint4* p = PK ? (const uint4*)((const uint2*)a + i) : (const uint4*)a + i;
+#pragma unroll
+        for (int k = 0; k < W4; k++) w[k] = p[k];
+    }
+    static __device__ __forceinline__ void unpack4(const uint4 (&w)[W4], uint4 (&o)[4]) {
+        if (PK) {
+#pragma unroll
+            for (int k = 0; k < 2; k++) { o[2 * k] = pk_unpack(make_uint2(w[k].x, w[k].y)); o[2 * k + 1] = pk_unpack(make_uint2(w[k].z, w[k].w)); }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) o[k] = w[k % W4];
+        }
+    }
+    __device__ __forceinline__ void load4(size_t i, uint4 (&o)[4]) const { uint4 w[W4]; load4w(i, w); unpack4(w, o); }
+};
+
 // u = q - r', r' the strand-signed reference position (-r on the reverse strand): the anchor's diagonal. With it the gap of a
 // pair is |ux - uy| and dr = dq - (ux - uy): three instructions fewer per (anchor, predecessor) pair than from q and r.
 struct LaneAnchor { uint32_t q, u, m; int32_t f; };

@@ -71,7 +71,10 @@ template <class T> struct Strided {
 };
 
 struct ChainArgs {
-    const uint4* anc;      // anchors, array of (q pos, r pos, ref contig << 1 | reverse_match, q contig): a lane's chunk is one contiguous run of 16-byte records
+    // anchors: a lane's chunk is one contiguous run of them. 16-byte records (q pos, r pos, ref contig << 1 | reverse_match, q contig), or - after the slice join, the DP
+    // kernels' PK instances - 8-byte ones (q pos - the q pos of the chunk's head, ref contig << 1 | reverse_match; r pos: chain_dev.h pk_anchor) in the same space
+    const uint4* anc;
+    const uint2* row_q0;   // 8-byte anchors: per chunk-table row (indexed like chunks) the q pos and q contig of the chunk's head; null with 16-byte records
     const uint2* chunks; const uint32_t* n_chunks; const uint32_t* cbase; uint32_t n_pairs, n_rows;
     const uint32_t* row_pair;   // pair of every row of the chunk table
     const uint32_t* row_order;  // rows by chunk length, longest first, rows without a chunk last (null: table order) - the DP kernels that put several chunks in a wave
@@ -262,16 +265,17 @@ __global__ __launch_bounds__(64) void chunk_hops_sliced_kernel(const uint32_t* _
 __global__ __launch_bounds__(64) void chunk_hops_items_kernel(const uint32_t* __restrict__ pstart, const uint32_t* __restrict__ aoff,
                                                                const PairDesc* __restrict__ pairs, const uint32_t* __restrict__ sbase, const uint32_t* __restrict__ cbase,
                                                                uint32_t n_pairs, uint32_t* __restrict__ slice_cnt, uint2* __restrict__ scratch, uint32_t* __restrict__ err);
-__global__ __launch_bounds__(64 * LANE_WAVES) __attribute__((amdgpu_waves_per_eu(3, 8))) void chain_lane20_kernel(ChainArgs A, uint32_t rows_per_wave);
-__global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane20x_kernel(ChainArgs A, uint32_t rows_per_wave);
-__global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane_kernel(ChainArgs A, uint32_t rows_per_wave);
-__global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_kernel(ChainArgs A);
-__global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_deep_kernel(ChainArgs A);
-__global__ __launch_bounds__(64 * CHAIN_WAVES) void chain_chunk_kernel(ChainArgs A);
-__global__ __launch_bounds__(64 * CHAIN_WAVES) void chain_chunk_list_kernel(ChainArgs A);
+// the DP kernels: PK = the slice join's 8-byte anchors (ChainArgs::anc), else the 16-byte records
+template <bool PK> __global__ __launch_bounds__(64 * LANE_WAVES) __attribute__((amdgpu_waves_per_eu(3, 8))) void chain_lane20_kernel(ChainArgs A, uint32_t rows_per_wave);
+template <bool PK> __global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane20x_kernel(ChainArgs A, uint32_t rows_per_wave);
+template <bool PK> __global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane_kernel(ChainArgs A, uint32_t rows_per_wave);
+template <bool PK> __global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_kernel(ChainArgs A);
+template <bool PK> __global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_deep_kernel(ChainArgs A);
+template <bool PK> __global__ __launch_bounds__(64 * CHAIN_WAVES) void chain_chunk_kernel(ChainArgs A);
+template <bool PK> __global__ __launch_bounds__(64 * CHAIN_WAVES) void chain_chunk_list_kernel(ChainArgs A);
 __global__ __launch_bounds__(256) void row_len_kernel(const uint2* __restrict__ chunks, const uint32_t* __restrict__ n_chunks, const uint32_t* __restrict__ cbase,
                                                       const uint32_t* __restrict__ row_pair, uint32_t n_rows, uint32_t* __restrict__ key, uint32_t* __restrict__ val);
-template <int S>
+template <int S, bool PK>
 __global__ __launch_bounds__(64 * CHAIN_WAVES) void chain_wave_reg_kernel(ChainArgs A);
 __global__ __launch_bounds__(256) void select_tiny_kernel(SelArgs S);
 __global__ __launch_bounds__(64) void select_kernel(SelArgs S, uint32_t* __restrict__ mid_list, uint32_t* __restrict__ mid_count);

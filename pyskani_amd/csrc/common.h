@@ -546,6 +546,7 @@ struct SketchConsts {
 // ---- the one-launch-sequence query of a small genome from host bytes (psk_query_host; small_query.hip) -------------------------
 // Fixed capacities: a call whose genome does not fit them takes the general path (psk_sketch_host + psk_query).
 constexpr int BSI_BLOG = 8;                 // references per block of the blocked seed index: 2^8
+constexpr uint32_t GSI_CONTIG_BITS = 15;    // the seed indexes' contig field (value bits 33..47): references of more than 2^15 contigs are not indexed
 constexpr uint32_t SQ_MAX_TILES = 64, SQ_MAX_DESC = 64;     // tiles of 16 384 bases / kept contigs of the query
 constexpr uint32_t SQ_SEEDS = 3072;        // query seeds, and anchors of one (query, reference) pair, the fused chain kernel holds in LDS
 constexpr uint32_t SQ_MARKERS = 2048;      // raw query markers the screen workgroup sorts in LDS

@@ -9,15 +9,18 @@
 
 // Serial restatement of the oracle's per-chunk body, run by ONE lane on global scratch. Used for
 // chunks the LDS path cannot hold (many chain trees / candidates) and as an in-GPU cross-check.
-__device__ uint32_t chain_chunk_serial(const ChainArgs& A, uint32_t s, uint32_t e) {
+// (PK: the slice join's 8-byte anchors, q relative to the row's head q0 - added back where a q position leaves)
+template <bool PK>
+__device__ uint32_t chain_chunk_serial(const ChainArgs& A, uint32_t s, uint32_t e, uint32_t q0) {
+    const AncRd<PK> an{A.anc};
     for (uint32_t x = s; x < e; x++) {
         int32_t bs = ANCHOR_SCORE2; uint32_t bp = x;
-        uint32_t qx = A.anc[x].x, rx = A.anc[x].y, mx = A.anc[x].z;
+        uint32_t qx = an[x].x, rx = an[x].y, mx = an[x].z;
         for (uint32_t y = x; y-- > s && x - y <= (uint32_t)A.band;) {
-            if (A.anc[y].z != mx) continue;
-            int64_t dq = (int64_t)qx - (int64_t)A.anc[y].x;
+            if (an[y].z != mx) continue;
+            int64_t dq = (int64_t)qx - (int64_t)an[y].x;
             if (dq > BP_CHAIN_BAND) break;
-            int64_t dr = (mx & 1) ? (int64_t)A.anc[y].y - (int64_t)rx : (int64_t)rx - (int64_t)A.anc[y].y;
+            int64_t dr = (mx & 1) ? (int64_t)an[y].y - (int64_t)rx : (int64_t)rx - (int64_t)an[y].y;
             if (dq <= 0 || dr <= 0) continue;
             int64_t gap = dq > dr ? dq - dr : dr - dq;
             if (gap > MAX_GAP_LENGTH) continue;
@@ -35,10 +38,10 @@ __device__ uint32_t chain_chunk_serial(const ChainArgs& A, uint32_t s, uint32_t 
         if (A.sc_root[x] != x) continue;
         uint32_t b = A.sc_best[x];
         if (A.sc_depth[b] < MIN_ANCHORS || A.sc_f[b] < MIN_SCORE2) continue;
-        uint32_t ra = A.anc[x].y, rb = A.anc[b].y;
-        A.c_score[s + nc] = A.sc_f[b]; A.c_q0[s + nc] = A.anc[x].x; A.c_q1[s + nc] = A.anc[b].x;
+        uint32_t ra = an[x].y, rb = an[b].y;
+        A.c_score[s + nc] = A.sc_f[b]; A.c_q0[s + nc] = an[x].x + q0; A.c_q1[s + nc] = an[b].x + q0;
         A.c_r0[s + nc] = ra < rb ? ra : rb; A.c_r1[s + nc] = ra < rb ? rb : ra; A.c_n[s + nc] = A.sc_depth[b];
-        A.c_rc[s + nc] = A.anc[x].z >> 1;
+        A.c_rc[s + nc] = an[x].z >> 1;
         nc++;
     }
     return nc;
@@ -56,7 +59,11 @@ __device__ uint32_t chain_chunk_serial(const ChainArgs& A, uint32_t s, uint32_t 
 // XT: further tree slots per lane in LDS (0, or LANE_XTREES for Gb-scale pairs: there a seed has ~6 chance 15-mer matches beside the
 // true one, the band of 20 ANCHORS reaches back only ~3 seeds, a true chain breaks wherever three seeds in a row do not match and a
 // chunk holds 5-15 qualifying trees - with four slots most chunks went to the wave-per-chunk kernel, 7.7 of 10 ms per 3 Gb pair)
-template <int W, int XT>      // window depth: the band rounded up to a multiple of four (20 at c = 125; 24 covers c >= 105)
+#ifndef LANE_PK_LD
+#define LANE_PK_LD 4
+#endif
+static_assert(LANE_PK_LD == 2 || LANE_PK_LD == 4, "eight or sixteen 8-byte anchors per load");
+template <int W, int XT, bool PK>      // window depth: the band rounded up to a multiple of four (20 at c = 125; 24 covers c >= 105); PK: the slice join's 8-byte anchors
 __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32_t rows_per_wave) {
     __shared__ uint32_t s_rd[LANE_WAVES][32][64];     // tree id << 14 | depth of the last 32 anchors, per lane
     __shared__ unsigned long long s_xk[LANE_WAVES][XT ? XT : 1][XT ? 64 : 1];     // slots 4 .. 4 + XT - 1: best anchor key
@@ -78,7 +85,9 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
     // LD = 2: a lane asks for 128 contiguous bytes - eight anchors, a whole cache line - per load and walks them as two steps of four: with 64 bytes per
     // load the other half of every line was fetched again a step later (the kernel's counters: 1.8 x its anchors' bytes, and once the far part of the band
     // is rarely scored that traffic, not the instruction count, is what the kernel waits for)
-    constexpr int LD = XT ? 1 : 2;
+    // With the slice join's 8-byte anchors (PK) a 128-byte line holds sixteen of them: LD = LANE_PK_LD (4: the line; 2: 64 bytes)
+    constexpr int LD = XT ? 1 : PK ? LANE_PK_LD : 2;
+    const AncRd<PK> anc{A.anc};
     const uint32_t s_al = s & ~(4u * LD - 1u);
     const uint32_t len = mine ? e - s_al : 0;          // steps this lane takes part in (the first s - s_al are idle)
     LanePred P[W];
@@ -105,18 +114,19 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
     constexpr int NR = LANE_NEAR;
     uint32_t far_diag = 0;
     for (uint32_t tb = 0; __any(tb < len); tb += 4 * LD) {
-      uint4 an[4 * LD];
+      uint4 aw[LD][AncRd<PK>::W4];      // the raw words; an anchor is decoded once, in its step
 #pragma unroll
-      for (int i = 0; i < 4 * LD; i++) an[i] = make_uint4(0, 0, 0, 0);
+      for (int h = 0; h < LD; h++) for (int i = 0; i < AncRd<PK>::W4; i++) aw[h][i] = make_uint4(0, 0, 0, 0);
       if (tb < len) {
 #pragma unroll
-          for (int i = 0; i < 4 * LD; i++) an[i] = A.anc[s_al + tb + i];      // (the array ends in 64 spare records)
+          for (int h = 0; h < LD; h++) anc.load4w(s_al + tb + 4u * h, aw[h]);      // (the array ends in 64 spare 16-byte records: 128 of the 8-byte ones)
       }
 #pragma unroll
       for (int h = 0; h < LD; h++) {
+        uint4 an4[4];      // (q, r, ref contig | strand, -)
+        AncRd<PK>::unpack4(aw[h], an4);
         const uint32_t t0 = tb + 4u * h, x0 = s_al + t0;
-        const uint32_t qs[4] = {an[4 * h].x, an[4 * h + 1].x, an[4 * h + 2].x, an[4 * h + 3].x}, rs[4] = {an[4 * h].y, an[4 * h + 1].y, an[4 * h + 2].y, an[4 * h + 3].y},
-                       ms[4] = {an[4 * h].z, an[4 * h + 1].z, an[4 * h + 2].z, an[4 * h + 3].z};
+        const uint32_t qs[4] = {an4[0].x, an4[1].x, an4[2].x, an4[3].x}, rs[4] = {an4[0].y, an4[1].y, an4[2].y, an4[3].y}, ms[4] = {an4[0].z, an4[1].z, an4[2].z, an4[3].z};
         LanePred nw[4];
         int32_t ftop[4] = {-1, -1, -1, -1};      // largest f - 1 among the far entries of the step's anchor u: P[NR - u .. W - 1]
         if (prune) {
@@ -204,6 +214,7 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
         if (mine && !ovf) {
             // candidates in ROOT order (slots were taken in order of first qualifying anchor): pick the smallest root left
             uint32_t nc = 0, last = 0;
+            const uint32_t q0 = PK ? A.row_q0[slot].x : 0u;      // (8-byte anchors: q positions leave absolute)
             for (uint32_t c = 0; c < S; c++) {
                 uint32_t pick = 0xFFFFFFFFu; unsigned long long k = 0;
 #pragma unroll
@@ -216,11 +227,12 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
                     }
                 last = pick;
                 const uint32_t xb = s + (16383u - (uint32_t)((k >> 14) & 16383u));      // the tree's best anchor
-                const uint32_t q1 = A.anc[xb].x, rb = A.anc[xb].y;
-                const uint32_t xr = s + pick, ra = A.anc[xr].y, o = s + nc;
-                A.c_score[o] = (int32_t)(uint32_t)(k >> 28); A.c_q0[o] = A.anc[xr].x; A.c_q1[o] = q1;
+                const uint4 ab = anc[xb], ar = anc[s + pick];
+                const uint32_t q1 = ab.x + q0, rb = ab.y;
+                const uint32_t ra = ar.y, o = s + nc;
+                A.c_score[o] = (int32_t)(uint32_t)(k >> 28); A.c_q0[o] = ar.x + q0; A.c_q1[o] = q1;
                 A.c_r0[o] = ra < rb ? ra : rb; A.c_r1[o] = ra < rb ? rb : ra;
-                A.c_n[o] = (uint32_t)(k & 16383u); A.c_rc[o] = A.anc[xr].z >> 1;
+                A.c_n[o] = (uint32_t)(k & 16383u); A.c_rc[o] = ar.z >> 1;
                 nc++;
             }
             ChunkOut o{};
@@ -234,9 +246,12 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
 
 // W = 20 fits three waves per SIMD (168 registers; the 24-deep window needs 192 and runs two): the kernel is VALU-issue bound and
 // a third wave fills issue slots that two leave empty
-__global__ __launch_bounds__(64 * LANE_WAVES) __attribute__((amdgpu_waves_per_eu(3, 8))) void chain_lane20_kernel(ChainArgs A, uint32_t rows_per_wave) { chain_lane_body<20, 0>(A, rows_per_wave); }
-__global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane20x_kernel(ChainArgs A, uint32_t rows_per_wave) { chain_lane_body<20, LANE_XTREES>(A, rows_per_wave); }
-__global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane_kernel(ChainArgs A, uint32_t rows_per_wave) { chain_lane_body<LANE_N, 0>(A, rows_per_wave); }
+template <bool PK>
+__global__ __launch_bounds__(64 * LANE_WAVES) __attribute__((amdgpu_waves_per_eu(3, 8))) void chain_lane20_kernel(ChainArgs A, uint32_t rows_per_wave) { chain_lane_body<20, 0, PK>(A, rows_per_wave); }
+template <bool PK>
+__global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane20x_kernel(ChainArgs A, uint32_t rows_per_wave) { chain_lane_body<20, LANE_XTREES, PK>(A, rows_per_wave); }
+template <bool PK>
+__global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane_kernel(ChainArgs A, uint32_t rows_per_wave) { chain_lane_body<LANE_N, 0, PK>(A, rows_per_wave); }
 
 // ---- four lanes per chunk, for launches too small to fill the chip with one lane per chunk -----------------
 // (the headline search: 100 pairs = 22 k chunks). Lane j of a quad owns the anchors whose index is j mod 4: ownership
@@ -257,7 +272,9 @@ __device__ __forceinline__ uint32_t lane_eval_d(uint32_t qx, uint32_t ux, uint32
     return ((((uint32_t)scp << 7) + (((uint32_t)ANCHOR_SCORE2 << 7) | 127u) - d)) & ok;
 }
 
+template <bool PK>
 __global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_kernel(ChainArgs A) {
+    const AncRd<PK> anc{A.anc};
     __shared__ uint32_t s_rd[LANE_WAVES][32][16];     // root index << 14 | depth of the last 32 anchors, per quad
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, quad = lane >> 2;
     const uint32_t j = lane & 3;
@@ -289,9 +306,9 @@ __global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_kernel(ChainArgs A
     const int band = A.band;
     for (uint32_t t0 = 0; __any(t0 < len); t0 += 4) {
         const uint32_t x0 = s_al + t0;
-        uint4 an0 = make_uint4(0, 0, 0, 0), an1 = an0, an2 = an0, an3 = an0;
-        if (t0 < len) { an0 = A.anc[x0]; an1 = A.anc[x0 + 1]; an2 = A.anc[x0 + 2]; an3 = A.anc[x0 + 3]; }      // 64 contiguous bytes per lane
-        const uint32_t qs[4] = {an0.x, an1.x, an2.x, an3.x}, rs[4] = {an0.y, an1.y, an2.y, an3.y}, ms[4] = {an0.z, an1.z, an2.z, an3.z};
+        uint4 an[4] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+        if (t0 < len) anc.load4(x0, an);      // 64 (8-byte anchors: 32) contiguous bytes per lane
+        const uint32_t qs[4] = {an[0].x, an[1].x, an[2].x, an[3].x}, rs[4] = {an[0].y, an[1].y, an[2].y, an[3].y}, ms[4] = {an[0].z, an[1].z, an[2].z, an[3].z};
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const uint32_t x = x0 + u, t = t0 + u;
@@ -345,16 +362,18 @@ __global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_kernel(ChainArgs A
     if (j == 0 && slot < A.n_rows && real) {
         if (mine && !ovf) {
             uint32_t nc = 0, last = 0;
+            const uint32_t q0 = PK ? A.row_q0[slot].x : 0u;      // (8-byte anchors: q positions leave absolute)
             for (uint32_t c = 0; c < S; c++) {
                 uint32_t pick = 0xFFFFFFFFu; unsigned long long k = 0; uint32_t q1 = 0, rb = 0;
 #pragma unroll
                 for (int i = 0; i < LANE_TREES; i++)
                     if (sroot[i] != 0xFFFFFFFFu && (c == 0 || sroot[i] > last) && sroot[i] < pick) { pick = sroot[i]; k = bk[i]; q1 = bq[i]; rb = br[i]; }
                 last = pick;
-                const uint32_t xr = s + pick, ra = A.anc[xr].y, o = s + nc;
-                A.c_score[o] = (int32_t)(uint32_t)(k >> 28); A.c_q0[o] = A.anc[xr].x; A.c_q1[o] = q1;
+                const uint4 ar = anc[s + pick];
+                const uint32_t ra = ar.y, o = s + nc;
+                A.c_score[o] = (int32_t)(uint32_t)(k >> 28); A.c_q0[o] = ar.x + q0; A.c_q1[o] = q1 + q0;
                 A.c_r0[o] = ra < rb ? ra : rb; A.c_r1[o] = ra < rb ? rb : ra;
-                A.c_n[o] = (uint32_t)(k & 16383u); A.c_rc[o] = A.anc[xr].z >> 1;
+                A.c_n[o] = (uint32_t)(k & 16383u); A.c_rc[o] = ar.z >> 1;
                 nc++;
             }
             ChunkOut o{};
@@ -387,7 +406,9 @@ __device__ __forceinline__ int32_t quad_eval(uint32_t qx, uint32_t ux, uint32_t 
     const uint32_t key = ((uint32_t)s1 << 7) + (((((uint32_t)ANCHOR_SCORE2 + 1u) << 7) | 127u) - (uint32_t)dpj);      // + j after the lane's maximum
     return (int32_t)(key | (bad & 0x80000000u));
 }
+template <bool PK>
 __global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_deep_kernel(ChainArgs A) {      // (255 registers, two waves per SIMD: capped at 168 it spills 83 dwords per lane)
+    const AncRd<PK> anc{A.anc};
     __shared__ uint32_t s_rd[LANE_WAVES][QD_RING][16];     // root index << 14 | depth of the last QD_RING anchors, per quad
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, quad = lane >> 2;
     const int32_t j = lane & 3;
@@ -420,9 +441,9 @@ __global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_deep_kernel(ChainA
     uint32_t far_diag = 0;
     for (uint32_t t0 = 0; __any(t0 < len); t0 += 4) {
         const uint32_t x0 = s_al + t0;
-        uint4 an0 = make_uint4(0, 0, 0, 0), an1 = an0, an2 = an0, an3 = an0;
-        if (t0 < len) { an0 = A.anc[x0]; an1 = A.anc[x0 + 1]; an2 = A.anc[x0 + 2]; an3 = A.anc[x0 + 3]; }      // 64 contiguous bytes per lane
-        const uint32_t qs[4] = {an0.x, an1.x, an2.x, an3.x}, rs[4] = {an0.y, an1.y, an2.y, an3.y}, ms[4] = {an0.z, an1.z, an2.z, an3.z};
+        uint4 an[4] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+        if (t0 < len) anc.load4(x0, an);      // 64 (8-byte anchors: 32) contiguous bytes per lane
+        const uint32_t qs[4] = {an[0].x, an[1].x, an[2].x, an[3].x}, rs[4] = {an[0].y, an[1].y, an[2].y, an[3].y}, ms[4] = {an[0].z, an[1].z, an[2].z, an[3].z};
         uint32_t nq = 0, nu = 0, nm = 0xFFFFFFFFu; int32_t nf = -1;      // this lane's own anchor of the step (from u = j on)
         // The FAR part of the window - a lane's entries QD_NEAR .. QD - 1: the quad's anchors more than 4 QD_NEAR + 3 back - can only win with a score above the
         // best near one: a predecessor y scores f[y] + ANCHOR_SCORE2 - gap <= f[y] + ANCHOR_SCORE2, and on equal scores the NEARER one is taken. far_top =
@@ -524,16 +545,18 @@ __global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_deep_kernel(ChainA
     if (j == 0 && slot < A.n_rows && real) {
         if (mine && !ovf) {
             uint32_t nc = 0, last = 0;
+            const uint32_t q0 = PK ? A.row_q0[slot].x : 0u;      // (8-byte anchors: q positions leave absolute)
             for (uint32_t c = 0; c < S; c++) {
                 uint32_t pick = 0xFFFFFFFFu; unsigned long long k = 0; uint32_t q1 = 0, rb = 0;
 #pragma unroll
                 for (int i = 0; i < LANE_TREES; i++)
                     if (sroot[i] != 0xFFFFFFFFu && (c == 0 || sroot[i] > last) && sroot[i] < pick) { pick = sroot[i]; k = bk[i]; q1 = bq[i]; rb = br[i]; }
                 last = pick;
-                const uint32_t xr = s + pick, ra = A.anc[xr].y, o = s + nc;
-                A.c_score[o] = (int32_t)(uint32_t)(k >> 28); A.c_q0[o] = A.anc[xr].x; A.c_q1[o] = q1;
+                const uint4 ar = anc[s + pick];
+                const uint32_t ra = ar.y, o = s + nc;
+                A.c_score[o] = (int32_t)(uint32_t)(k >> 28); A.c_q0[o] = ar.x + q0; A.c_q1[o] = q1 + q0;
                 A.c_r0[o] = ra < rb ? ra : rb; A.c_r1[o] = ra < rb ? rb : ra;
-                A.c_n[o] = (uint32_t)(k & 16383u); A.c_rc[o] = A.anc[xr].z >> 1;
+                A.c_n[o] = (uint32_t)(k & 16383u); A.c_rc[o] = ar.z >> 1;
                 nc++;
             }
             ChunkOut o{};
@@ -569,9 +592,12 @@ struct ChainWaveLds {
 };
 static_assert(sizeof(uint32_t) * 7 * 64 <= sizeof(uint32_t) * 6 * RING, "candidate staging fits the ring");
 
-__device__ void chain_row_candidates(const ChainArgs& A, uint32_t s, uint32_t e, ChunkOut* op, ChainWaveLds& L, int lane, uint32_t R, bool fast);
+template <bool PK>
+__device__ void chain_row_candidates(const ChainArgs& A, uint32_t slot, uint32_t s, uint32_t e, ChunkOut* op, ChainWaveLds& L, int lane, uint32_t R, bool fast);
 
+template <bool PK>
 __device__ void chain_chunk_row(const ChainArgs& A, uint32_t slot, ChainWaveLds& L, int lane) {
+    const AncRd<PK> anc{A.anc};
     const uint2 se = A.chunks[slot];
     const uint32_t s = se.x, e = se.y, n = e - s;
     ChunkOut* op = &A.out[slot];
@@ -583,7 +609,7 @@ __device__ void chain_chunk_row(const ChainArgs& A, uint32_t slot, ChainWaveLds&
         for (uint32_t base = s; base < e && fast; base += 64) {
             const uint32_t idx = base + lane;
             const bool have = idx < e;
-            const uint4 my_a = have ? A.anc[idx] : make_uint4(0, 0, 0, 0);
+            const uint4 my_a = have ? anc[idx] : make_uint4(0, 0, 0, 0);
             const uint32_t my_qp = my_a.x, my_rp = my_a.y, my_rm = my_a.z;
             const uint32_t cnt = e - base < 64 ? e - base : 64;
             for (uint32_t j = 0; j < cnt; j++) {
@@ -633,12 +659,15 @@ __device__ void chain_chunk_row(const ChainArgs& A, uint32_t slot, ChainWaveLds&
             }
         }
     }
-    chain_row_candidates(A, s, e, op, L, lane, R, fast);
+    chain_row_candidates<PK>(A, slot, s, e, op, L, lane, R, fast);
 }
 
 // the chunk's candidate chains out of the per-tree bests in L.best[0 .. R) (fast), or the lane-serial path over global scratch (!fast)
-__device__ void chain_row_candidates(const ChainArgs& A, uint32_t s, uint32_t e, ChunkOut* op, ChainWaveLds& L, int lane, uint32_t R, bool fast) {
+template <bool PK>
+__device__ void chain_row_candidates(const ChainArgs& A, uint32_t slot, uint32_t s, uint32_t e, ChunkOut* op, ChainWaveLds& L, int lane, uint32_t R, bool fast) {
     unsigned long long* s_best_w = L.best; uint32_t (*s_cand_w)[64] = L.cand;
+    const AncRd<PK> anc{A.anc};
+    const uint32_t q0 = PK ? A.row_q0[slot].x : 0u;      // (8-byte anchors: q positions leave absolute)
     uint32_t C = 0;
     if (fast) {
         // candidates: one per chain tree whose best anchor passes the thresholds, in root order
@@ -656,17 +685,17 @@ __device__ void chain_row_candidates(const ChainArgs& A, uint32_t s, uint32_t e,
             C += __popcll(bal);
             if (C > 64) { fast = false; break; }
             if (qual) {
-                uint32_t xr = s + rootx, xb = s + lx;
-                uint32_t ra = A.anc[xr].y, rb = A.anc[xb].y;
-                s_cand_w[0][ci] = f; s_cand_w[1][ci] = A.anc[xr].x; s_cand_w[2][ci] = A.anc[xb].x;
+                const uint4 ar = anc[s + rootx], ab = anc[s + lx];
+                uint32_t ra = ar.y, rb = ab.y;
+                s_cand_w[0][ci] = f; s_cand_w[1][ci] = ar.x + q0; s_cand_w[2][ci] = ab.x + q0;
                 s_cand_w[3][ci] = ra < rb ? ra : rb; s_cand_w[4][ci] = ra < rb ? rb : ra; s_cand_w[5][ci] = dep;
-                s_cand_w[6][ci] = A.anc[xr].z >> 1;
+                s_cand_w[6][ci] = ar.z >> 1;
             }
         }
     }
     if (!fast) {   // lane-serial path writes its candidates straight to the global arrays
         if (lane == 0) {
-            C = chain_chunk_serial(A, s, e);
+            C = chain_chunk_serial<PK>(A, s, e, q0);
             atomicAdd(&A.stats[1], 1u);
         }
     } else {
@@ -685,6 +714,7 @@ __device__ void chain_row_candidates(const ChainArgs& A, uint32_t s, uint32_t e,
 }
 
 // every row of the chunk table (used when the lane kernel does not run: band > LANE_N, PSK_CHAIN_LANE=0, serial cross-check)
+template <bool PK>
 __global__ __launch_bounds__(64 * CHAIN_WAVES) void chain_chunk_kernel(ChainArgs A) {
     __shared__ ChainWaveLds s_lds[CHAIN_WAVES];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -692,16 +722,17 @@ __global__ __launch_bounds__(64 * CHAIN_WAVES) void chain_chunk_kernel(ChainArgs
     const uint32_t pair = A.row_pair[slot < A.n_rows ? slot : A.n_rows - 1];
     if (slot >= A.n_rows) return;
     if (slot - A.cbase[pair] >= A.n_chunks[pair]) return;
-    chain_chunk_row(A, slot, s_lds[wave], lane);
+    chain_chunk_row<PK>(A, slot, s_lds[wave], lane);
 }
 
 // only the rows the lane kernel listed (fixed grid, waves loop over the list: its length is known on the device only)
+template <bool PK>
 __global__ __launch_bounds__(64 * CHAIN_WAVES) void chain_chunk_list_kernel(ChainArgs A) {
     __shared__ ChainWaveLds s_lds[CHAIN_WAVES];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t n_list = *A.ovf_count, n_waves = gridDim.x * CHAIN_WAVES;
     for (uint32_t k = blockIdx.x * CHAIN_WAVES + wave; k < n_list; k += n_waves) {
-        chain_chunk_row(A, A.ovf_list[k], s_lds[wave], lane);
+        chain_chunk_row<PK>(A, A.ovf_list[k], s_lds[wave], lane);
         lds_wave_sync();
     }
 }
@@ -753,13 +784,13 @@ __device__ __forceinline__ uint32_t wave_max_scalar(uint32_t v) {
 }
 
 // one block of up to 64 anchors (chunk-local indices base - s ...): its anchors take register set T (compile time: no branch per anchor)
-template <int S, int T>
+template <int S, int T, bool PK>
 __device__ __forceinline__ void chain_reg_block(const ChainArgs& A, ChainWaveLds& L, uint32_t* s_root, const int lane, const uint32_t s, const uint32_t e, const uint32_t base,
                                                 const uint32_t band, RegWin& w0, RegWin& w1, uint32_t& R, bool& over) {
     constexpr uint32_t WMASK = 64u * S - 1u;
     RegWin& wt = T ? w1 : w0;
     const uint32_t idx = base + lane;
-    const uint4 my_a = idx < e ? A.anc[idx] : make_uint4(0, 0, 0, 0);
+    const uint4 my_a = idx < e ? AncRd<PK>{A.anc}[idx] : make_uint4(0, 0, 0, 0);
     const uint32_t cnt = e - base < 64 ? e - base : 64;
     for (uint32_t j = 0; j < cnt; j++) {
         const uint32_t qx = __builtin_amdgcn_readlane(my_a.x, j), rx = __builtin_amdgcn_readlane(my_a.y, j), mx = __builtin_amdgcn_readlane(my_a.z, j);
@@ -802,7 +833,7 @@ __device__ __forceinline__ void chain_reg_block(const ChainArgs& A, ChainWaveLds
         atomicMax(&L.best[wt.id], ((unsigned long long)(uint32_t)(wt.f1 + 1) << 28) | ((unsigned long long)(16383u - (base - s + (uint32_t)lane)) << 14) | wt.dp);
 }
 
-template <int S>
+template <int S, bool PK>
 __device__ void chain_chunk_row_reg(const ChainArgs& A, uint32_t slot, ChainWaveLds& L, int lane) {
     static_assert(S == 1 || S == 2, "one or two window slots per lane");
     const uint2 se = A.chunks[slot];
@@ -820,8 +851,8 @@ __device__ void chain_chunk_row_reg(const ChainArgs& A, uint32_t slot, ChainWave
         lds_wave_sync();
         bool over = false;
         for (uint32_t base = s; base < e && !over; base += 64u * S) {      // anchor a lives in lane a & 63 of register set (a >> 6) % S: blocks alternate between the sets
-            chain_reg_block<S, 0>(A, L, s_root, lane, s, e, base, band, w0, w1, R, over);
-            if (S > 1 && base + 64u < e && !over) chain_reg_block<S, 1>(A, L, s_root, lane, s, e, base + 64u, band, w0, w1, R, over);
+            chain_reg_block<S, 0, PK>(A, L, s_root, lane, s, e, base, band, w0, w1, R, over);
+            if (S > 1 && base + 64u < e && !over) chain_reg_block<S, 1, PK>(A, L, s_root, lane, s, e, base + 64u, band, w0, w1, R, over);
         }
         fast = !over;
     }
@@ -831,10 +862,10 @@ __device__ void chain_chunk_row_reg(const ChainArgs& A, uint32_t slot, ChainWave
         for (int u = 0; u < RMAX / 64; u++) if ((uint32_t)lane + 64u * u < R) L.best[lane + 64 * u] |= (unsigned long long)s_root[lane + 64 * u] << 49;      // the root's index rides in the top bits
         lds_wave_sync();
     }
-    chain_row_candidates(A, s, e, op, L, lane, R, fast);
+    chain_row_candidates<PK>(A, slot, s, e, op, L, lane, R, fast);
 }
 
-template <int S>
+template <int S, bool PK>
 __global__ __launch_bounds__(64 * CHAIN_WAVES) void chain_wave_reg_kernel(ChainArgs A) {
     __shared__ ChainWaveLds s_lds[CHAIN_WAVES];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;      // (told to be uniform: the row's bounds, the loop counters and the tree count live in scalar registers)
@@ -842,10 +873,17 @@ __global__ __launch_bounds__(64 * CHAIN_WAVES) void chain_wave_reg_kernel(ChainA
     const uint32_t pair = A.row_pair[slot < A.n_rows ? slot : A.n_rows - 1];
     if (slot >= A.n_rows) return;
     if (slot - A.cbase[pair] >= A.n_chunks[pair]) return;
-    chain_chunk_row_reg<S>(A, slot, s_lds[wave], lane);
+    chain_chunk_row_reg<S, PK>(A, slot, s_lds[wave], lane);
 }
 
 
-// (launched from chain.hip)
-template __global__ void chain_wave_reg_kernel<1>(ChainArgs A);
-template __global__ void chain_wave_reg_kernel<2>(ChainArgs A);
+// (launched from chain.hip: the 16-byte records of the per-pair and contig joins, and the slice join's 8-byte anchors)
+#define PSK_DP_FORMS(PK) \
+    template __global__ void chain_lane20_kernel<PK>(ChainArgs, uint32_t); template __global__ void chain_lane20x_kernel<PK>(ChainArgs, uint32_t); \
+    template __global__ void chain_lane_kernel<PK>(ChainArgs, uint32_t); template __global__ void chain_quad_kernel<PK>(ChainArgs); \
+    template __global__ void chain_quad_deep_kernel<PK>(ChainArgs); template __global__ void chain_chunk_kernel<PK>(ChainArgs); \
+    template __global__ void chain_chunk_list_kernel<PK>(ChainArgs); \
+    template __global__ void chain_wave_reg_kernel<1, PK>(ChainArgs); template __global__ void chain_wave_reg_kernel<2, PK>(ChainArgs);
+PSK_DP_FORMS(false)
+PSK_DP_FORMS(true)
+#undef PSK_DP_FORMS

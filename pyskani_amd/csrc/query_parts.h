@@ -82,6 +82,7 @@ constexpr size_t CHAIN_ANCHOR_WORDS = 14;      // u32 per anchor in Lane::q_d: t
 // device arrays of one chain launch sequence, carved from ctx->q_b
 struct ChainBufs {
     PairDesc* pairs; uint32_t *sbase, *cbase, *pstart; uint2* lbcnt; uint32_t* aoff; uint32_t* nch; uint2* chunks; ChunkOut* cout;
+    uint2* row_q0;      // per chunk-table row: q pos and q contig of the chunk's head (the slice join writes them beside its 8-byte anchors)
     psk_hit* hits; psk_hit* hits_sel; uint32_t* misc; uint32_t* ovf; unsigned long long* bsum; uint2* pair_qr; BatchQ* bq;
     uint32_t *blk_pair, *row_pair, *live, *big_list, *huge_list;
     uint32_t gi, gi_sum;      // 256-item tiles; entries of bsum

@@ -36,7 +36,7 @@ psk_status build_gsi(Lane* ctx, psk_db* db) {
     uint64_t N = 0; uint32_t maxn = 0;
     for (uint32_t i = 0; i < n; i++) {
         const psk_sketch* r = db->refs[i];
-        if (!r->has_seeds || r->contig_len.size() > 32768u || r->params.k != db->params.k || r->params.c != db->params.c) return PSK_OK;
+        if (!r->has_seeds || r->contig_len.size() > (1u << GSI_CONTIG_BITS) || r->params.k != db->params.k || r->params.c != db->params.c) return PSK_OK;
         const uint32_t ns = r->store ? (uint32_t)r->n_seeds : 0u;
         segs[i] = GsiSeg{ns ? r->store->seed_kmer + r->seed_off : nullptr, ns ? r->store->seed_pm + r->seed_off : nullptr, ns, (uint32_t)N};
         N += ns; maxn = std::max(maxn, ns);
@@ -105,7 +105,7 @@ psk_status build_bsi(Lane* ctx, psk_db* db) {
         uint64_t in_block = 0;
         for (uint32_t i = r0; i < r1; i++) {
             const psk_sketch* r = db->refs[i];
-            if (!r->has_seeds || r->contig_len.size() > 32768u || r->params.k != db->params.k || r->params.c != db->params.c) return PSK_OK;
+            if (!r->has_seeds || r->contig_len.size() > (1u << GSI_CONTIG_BITS) || r->params.k != db->params.k || r->params.c != db->params.c) return PSK_OK;
             const uint32_t ns = r->store ? (uint32_t)r->n_seeds : 0u;
             if (in_block + ns >= 0x7FFFFF00ull) return PSK_OK;      // (a block is one radix sort: 256 references of more than 8 M seeds each - 1 Gb at c = 125 - have none)
             segs[i] = GsiSeg{ns ? r->store->seed_kmer + r->seed_off : nullptr, ns ? r->store->seed_pm + r->seed_off : nullptr, ns, (uint32_t)in_block};

@@ -662,6 +662,6 @@ __global__ __launch_bounds__(256) void chunk_seeds_kernel(ChainArgs A) {
     const uint2 ch0 = A.chunks[row];
     if (ch0.x > ch0.y || ch0.y > A.cap) return;
     const uint32_t nc = A.pairs[pair].q_nc;
-    const uint32_t qc = nc == 1u ? 0u : A.anc[ch0.x].w;      // (a one-contig query - most complete bacterial genomes - needs no look at the chunk's anchors: a cold 64-byte line per row)
+    const uint32_t qc = nc == 1u ? 0u : A.row_q0 ? A.row_q0[row].y : A.anc[ch0.x].w;      // (a one-contig query - most complete bacterial genomes - needs no look at the chunk's anchors: a cold 64-byte line per row; 8-byte anchors carry no q contig: the row's head does)
     if (qc < nc) o->seeds = seeds_between(A.pairs[pair], qc, o->left, o->right);
 }

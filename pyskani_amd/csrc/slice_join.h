@@ -32,9 +32,10 @@ struct GslArgs {
                          // lim1 = (key of the chunk head open at the slice's start) + 1 + FRAGMENT_LENGTH, 0 before the pair's first anchor (key = q contig << 32 | q pos)
     uint32_t* bm;        // per record GSL_WORDS words: the slice's seeds that have an anchor with the pair (count walk)
     uint32_t* pair_cnt;  // per pair: anchors (count walk, atomics over the slices)
-    const uint32_t* pstart; uint4* anc; uint32_t cap; uint32_t* err;      // err = the launch sequence's status words (bit 0: chunk table overflow, bit 1: capacity; [5]: rerun wide; [16..17]: 64-bit anchor total)
+    const uint32_t* pstart; uint2* anc; uint32_t cap; uint32_t* err;      // anc: 8-byte anchors (chain_dev.h pk_anchor); err = the launch sequence's status words (bit 0: chunk table overflow, bit 1: capacity; [5]: rerun wide; [16..17]: 64-bit anchor total)
     uint32_t p_cap;      // most pairs any entry of the batch holds, rounded up to 64
     uint2* chunks; uint32_t* n_chunks;
+    uint2* row_q0;       // per chunk-table row (indexed like chunks): q pos and q contig of the chunk's head - what the 8-byte anchors' q positions are relative to
 };
 
 // wave table of a batch: (entry, slice) for every slice of every entry's query, a query's slices one after the other; ebase: per entry (first record, first slice)

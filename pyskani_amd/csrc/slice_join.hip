@@ -16,12 +16,14 @@
 //   gsl_heads_kernel        per pair, slice after slice: first anchor of every (pair, slice), and - from the bitmaps - which seeds head
 //                           a CHUNK (a chunk = the anchors of one query contig within FRAGMENT_LENGTH of its first anchor - a property of
 //                           the query's seed positions, so no anchor is read for it): the rows before, and the head open at, every slice
-//   gsl_walk_kernel<true>   EMIT: the same walk writes the 16-byte anchors, every pair's through a 64-byte line staged in LDS, so
-//                           that they leave as whole lines (a scattered 16-byte store costs 32 bytes of HBM write traffic), and the chunk
-//                           table's rows as it meets the heads
+//   gsl_walk_kernel<true>   EMIT: the same walk writes the anchors, every pair's through a 32-byte line staged in LDS, so that they
+//                           leave as whole lines (a scattered store costs 32 bytes of HBM write traffic), and the chunk table's rows -
+//                           with the q pos and q contig of every row's head (row_q0) - as it meets the heads
 //
-// Bit-exactness: the anchors and chunk tables are the ones anchor_emit_pairs_kernel / chunk_heads_kernel produce (same order, same
-// rows); everything downstream (DP, selection, reduce) is unchanged.
+// The anchors are 8 bytes (chain_dev.h pk_anchor: q pos relative to the head of its chunk, ref contig << 1 | strand, r pos) where the
+// per-pair joins write 16-byte (q pos, r pos, ref contig << 1 | strand, q contig) records: the emit writes, and the DP reads, half the
+// bytes. Bit-exactness: the anchors and chunk tables are the ones anchor_emit_pairs_kernel / chunk_heads_kernel produce (same order, same
+// rows, the same anchors in the packed form); the DP kernels' PK instances add the rows' heads back, so the candidates are the same.
 #include "slice_join.h"
 #include "chain_dev.h"
 
@@ -42,10 +44,12 @@ void gsl_make_tab(const BatchQ* bq, size_t n_entries, const uint32_t* q_seeds, s
     for (size_t e = 0; e < n_entries; e++) for (uint32_t sl = 0; sl < (q_seeds[e] + GSL_SEEDS - 1) / GSL_SEEDS; sl++) tab.push_back(make_uint2((uint32_t)e, sl));
 }
 
-// LDS of one walk wave, the 16-byte units first: [EMIT: 4 x p_cap staged anchors][EMIT: lim1 per pair: p_cap x 8][EMIT: (cursor, first anchor) per pair, the step's lines]
+// LDS of one walk wave, the 16-byte units first: [EMIT: GSL_LW x p_cap staged 8-byte anchors][EMIT: lim1 per pair: p_cap x 8][EMIT: (cursor, first anchor) per pair, the step's lines]
 // [the walked block's pass row as eight (32 bits, prefix count) entries]
 // [COUNT: cursors: p_cap x 4; anchor-seed bitmaps, GSL_WORDS rows of p_cap + 1 words | EMIT: (cursor, first anchor) per pair: p_cap x 8; rows so far per pair: p_cap x 4]
-// anchors per staged line of the emit walk (GSL_LINE_N = 4: whole 64-byte lines; 2: 32-byte halves - half the LDS per wave, two more waves per SIMD)
+// anchors per staged line of the emit walk (GSL_LINE_N = 4: 32-byte lines, the smallest a write costs; 8: whole 64-byte lines - twice the LDS per wave). With 8-byte
+// anchors, 4 leaves a wave 13.9 instead of 22.1 KB at 256 pairs: eleven instead of seven waves per CU; measured on the 10 000 x 10 000 step, the emit walk alone
+// (rocprofv3 kernel trace) 374.8 against 598.6 ms over its 150 launches, the step 501-507 against 505-508 ms (profiles/r7)
 #ifndef GSL_LINE_N
 #define GSL_LINE_N 4
 #endif
@@ -54,7 +58,7 @@ static_assert(GSL_LW == 8 || GSL_LW == 4 || GSL_LW == 2, "a staged line holds ei
 static size_t gsl_walk_lds(const GslArgs& A, bool emit) {
     const size_t nw = (A.n_refs + 63) / 64;
     (void)nw;
-    return (emit ? (16 * GSL_LW + 8 + 8) * (size_t)A.p_cap + 8 * 64 : 0) + 64 + 4 * (size_t)A.p_cap + (emit ? 0 : 4 * (size_t)GSL_WORDS * (A.p_cap + 1));
+    return (emit ? (8 * GSL_LW + 8 + 8) * (size_t)A.p_cap + 8 * 64 : 0) + 64 + 4 * (size_t)A.p_cap + (emit ? 0 : 4 * (size_t)GSL_WORDS * (A.p_cap + 1));
 }
 
 // (streaming - nontemporal - stores of the anchors were measured on the 10 000 x 10 000 step: the walk takes the same time and the DP kernel that reads the anchors next 178 instead of
@@ -74,8 +78,8 @@ __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
     const uint32_t P = B.rank_hi - B.rank_lo, pc = A.p_cap;
     const uint2 eb = A.ebase[te.x];
     const uint32_t rec0 = eb.x + te.y * P;
-    uint4* s_line = s_gsl;                                                                  // EMIT: slot t of pair j at [t * pc + j]
-    unsigned long long* s_lim = (unsigned long long*)(s_gsl + (EMIT ? GSL_LW * pc : 0u));       // EMIT: lim1 of the pair's open chunk
+    uint2* s_line = (uint2*)s_gsl;                                                          // EMIT: slot t of pair j at [t * pc + j]
+    unsigned long long* s_lim = (unsigned long long*)(s_line + (EMIT ? GSL_LW * pc : 0u));     // EMIT: lim1 of the pair's open chunk
     uint2* s_cs = (uint2*)(s_lim + (EMIT ? pc : 0u));                                       // EMIT: (cursor, first anchor of the (pair, slice)): one 8-byte read
     uint2* s_fl = s_cs + (EMIT ? pc : 0u);                                                  // EMIT: the step's complete lines (pair | first slot << 16, first anchor of the line)
     uint2* s_bp = s_fl + (EMIT ? 64u : 0u);                                                 // the block being walked: its 256 references of the query's pass row, 32 per entry: (bits, passing references before them)
@@ -180,34 +184,39 @@ __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
                     continue;
                 }
                 const uint32_t sqp = (uint32_t)__builtin_amdgcn_readlane((int)qp, (int)s), sqm = (uint32_t)__builtin_amdgcn_readlane((int)qm, (int)s);
-                const uint32_t rmeta = (uint32_t)((((v >> 33) & 0x7FFFull) << 1) | (v & 1ull));      // ref contig << 1 | (fwd < rc)
-                const uint4 av = make_uint4(sqp, (uint32_t)(v >> 1), (rmeta & ~1u) | ((rmeta ^ sqm) & 1u), sqm >> 1);
+                const uint32_t rmeta = (uint32_t)((((v >> 33) & ((1ull << GSI_CONTIG_BITS) - 1ull)) << 1) | (v & 1ull));      // ref contig << 1 | (fwd < rc)
                 const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)slot, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);      // (lane 0: no lane before it)
                 const bool same = valid && prev == slot;      // not the first lane of its (seed, reference) group
                 const bool dup = __ballot(same) != 0;
                 const uint2 cs = s_cs[valid ? slot : 0u];      // (every lane reads - no branch around the read)
+                const unsigned long long lim = s_lim[valid ? slot : 0u];      // (the open head's key + 1 + FRAGMENT_LENGTH: its q pos is what the anchor's is stored relative to)
                 const uint32_t base = cs.x;
                 // chunk table: the group's first lane opens a new chunk when the seed's key is beyond the reach of the pair's open head (chunk_heads_kernel's rule; a
-                // group cut by a step boundary meets its own head again: not beyond) - the new row's first anchor and, with it, the end of the row before
+                // group cut by a step boundary meets its own head again: not beyond) - the new row's first anchor and, with it, the end of the row before. Every lane of
+                // the group takes the same decision from the same key and lim (read above, before the first lane writes), so all of them see the head they belong to
+                bool opens = false;
                 if (((uint32_t)__builtin_amdgcn_readlane((int)unw, (int)(jl >> 5)) >> (jl & 31u)) & 1u) {
-                    if (valid && !same) {
-                        const unsigned long long key1 = (((unsigned long long)(sqm >> 1) << 32) | sqp) + 1ull;
-                        if (key1 > s_lim[slot]) {
-                            const uint32_t row = s_rows[slot], idxc = base < A.cap ? base : A.cap;
-                            if (row < Q.rows) {
-                                uint2* r = A.chunks + ((size_t)B.row_off + (size_t)slot * Q.rows + row);
-                                r->x = idxc;
-                                if (row > 0) r[-1].y = idxc;
-                            } else atomicOr(A.err, 1u);
-                            s_rows[slot] = row + 1u; s_lim[slot] = key1 + FRAGMENT_LENGTH;
-                        }
+                    const unsigned long long key1 = (((unsigned long long)(sqm >> 1) << 32) | sqp) + 1ull;
+                    opens = valid && key1 > lim;
+                    if (opens && !same) {
+                        const uint32_t row = s_rows[slot], idxc = base < A.cap ? base : A.cap;
+                        if (row < Q.rows) {
+                            const size_t ri = (size_t)B.row_off + (size_t)slot * Q.rows + row;
+                            uint2* r = A.chunks + ri;
+                            r->x = idxc;
+                            if (row > 0) r[-1].y = idxc;
+                            A.row_q0[ri] = make_uint2(sqp, sqm >> 1);
+                        } else atomicOr(A.err, 1u);
+                        s_rows[slot] = row + 1u; s_lim[slot] = key1 + FRAGMENT_LENGTH;
                     }
                 }
+                const uint32_t q_rel = opens ? 0u : sqp - (uint32_t)(lim - 1ull - FRAGMENT_LENGTH);      // (a pair without a chunk table - lim all ones - has anchors no DP reads)
+                const uint2 av = pk_anchor(q_rel, (uint32_t)(v >> 1), (rmeta & ~1u) | ((rmeta ^ sqm) & 1u));
                 if (!dup) {      // every valid lane has a pair of its own (a reference holds a k-mer once, nearly always): nothing to order between lanes
                     // (no capacity test on this path: the count walk's total was held against the capacity before this kernel started - see the guard at its top)
                     const uint32_t t3 = base & GSL_LM;
                     if (valid) { s_cs[slot].x = base + 1u; s_line[t3 * pc + slot] = av; }
-                    // complete lines leave TOGETHER: four consecutive lanes write one pair's 64 bytes (one request per line where a lane writing its own line makes four)
+                    // complete lines leave TOGETHER: GSL_LW consecutive lanes write one pair's line (one request per line where a lane writing its own line makes GSL_LW)
                     const bool fl = valid && t3 == GSL_LM;
                     const unsigned long long fm = __ballot(fl);
                     if (fm) {
