@@ -101,9 +101,10 @@ typedef struct { uint32_t kmer, pos, contig, canon; } psk_seed; /* export record
 const char* psk_last_error(void);
 const char* psk_version(void);
 /* The C-ABI's revision: raised whenever an entry point's parameters or a structure's layout change (4: psk_sketch_unpack takes the extent of its source buffer as third
- * argument; 5: psk_hit_min / psk_query_many_min / psk_gather_hits_min / psk_ctx_join_work added). A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
+ * argument; 5: psk_hit_min / psk_query_many_min / psk_gather_hits_min / psk_ctx_join_work added;
+ * 6: psk_db_locality added). A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
  * written against before it calls anything else: an argument list that moved is a memory error, not a link error. */
-#define PSK_ABI_VERSION 5
+#define PSK_ABI_VERSION 6
 int psk_abi_version(void);
 /* Releases an array the library returned (hit lists, gathered lists). Never release such an array with free(): large hit arrays are
  * huge-page blocks the library keeps one of for its next call ($PSK_HIT_CACHE=0: returned to the system at once). */
@@ -265,6 +266,13 @@ psk_status psk_db_add_batch(psk_db* db, const char* const* names, psk_sketch* co
 uint32_t psk_db_size(const psk_db* db);
 const char* psk_db_name(const psk_db* db, uint32_t index);
 const psk_sketch* psk_db_sketch(const psk_db* db, uint32_t index);
+
+/* The database's locality order: an internal order of the references in which relatives are neighbours (found on the GPU from the references' marker sets; the seed
+ * indexes are laid out by it, so the speed of the index joins does not depend on the order the references were added in). Nothing at this boundary is in that
+ * order - indices, names and hits stay in insertion order; this call computes the order if references were added since it was last computed and reports it:
+ * slot_of[i] = position of reference i (psk_db_size entries, or NULL), *n_groups = groups of relatives found, *is_identity = 1 when the order is the insertion
+ * order (the references' groups were contiguous already, the database fits one index block of 256 references, or $PSK_LOCALITY=0). Any pointer may be NULL. */
+psk_status psk_db_locality(psk_db* db, uint32_t* slot_of, uint32_t* n_groups, uint32_t* is_identity);
 
 /* check_markers_quickly(query, ref_i, screen_val, rescue_small) for every ref of the db.
  * pass[i] in {0,1}; shared[i] = |markers(q) ∩ markers(ref_i)| (may be NULL). */

@@ -426,7 +426,7 @@ void psk_db_destroy(psk_db* db) {
     for (psk_sketch* s : db->refs) delete s;
     db->d_marker_ptr.release(); db->d_marker_n.release();
     db->inv_key.release(); db->inv_ref.release(); db->inv_tmp.release(); db->inv_bucket.release();
-    db->d_refdesc.release(); db->d_canon.release();
+    db->d_refdesc.release(); db->d_canon.release(); db->d_refdesc_slot.release(); db->d_ref_of.release(); db->d_slot_of.release();
     db->gsi_key.release(); db->gsi_val.release(); db->gsi_bucket.release();
     db->bsi_key.release(); db->bsi_val.release(); db->bsi_bucket.release(); db->bsi_base.release();
     delete db;
@@ -439,8 +439,7 @@ psk_status psk_db_add(psk_db* db, const char* name, psk_sketch* s) {
     db->refs.push_back(s);
     db->names.emplace_back(name);
     db->note_added((uint32_t)db->refs.size() - 1);
-    db->tables_dirty = true; db->inv_dirty = true; db->desc_dirty = true; db->small_state = 0; db->gsi_key.release(); db->gsi_val.release(); db->gsi_bucket.release(); db->gsi_state = 0;
-    db->bsi_key.release(); db->bsi_val.release(); db->bsi_bucket.release(); db->bsi_base.release(); db->bsi_state = 0;
+    db->stale();
     return PSK_OK;
 }
 
@@ -454,8 +453,7 @@ psk_status psk_db_add_batch(psk_db* db, const char* const* names, psk_sketch* co
         db->names.emplace_back(names[i]);
         db->note_added((uint32_t)db->refs.size() - 1);
     }
-    db->tables_dirty = true; db->inv_dirty = true; db->desc_dirty = true; db->small_state = 0; db->gsi_key.release(); db->gsi_val.release(); db->gsi_bucket.release(); db->gsi_state = 0;
-    db->bsi_key.release(); db->bsi_val.release(); db->bsi_bucket.release(); db->bsi_base.release(); db->bsi_state = 0;
+    db->stale();
     return PSK_OK;
 }
 
@@ -463,6 +461,18 @@ psk_status psk_db_add_batch(psk_db* db, const char* const* names, psk_sketch* co
 uint32_t psk_db_size(const psk_db* db) { if (!db) return 0; std::shared_lock<std::shared_mutex> lk(db->rw); return (uint32_t)db->refs.size(); }
 const char* psk_db_name(const psk_db* db, uint32_t i) { if (!db) return nullptr; std::shared_lock<std::shared_mutex> lk(db->rw); return i < db->names.size() ? db->names[i].c_str() : nullptr; }
 const psk_sketch* psk_db_sketch(const psk_db* db, uint32_t i) { if (!db) return nullptr; std::shared_lock<std::shared_mutex> lk(db->rw); return i < db->refs.size() ? db->refs[i] : nullptr; }
+
+psk_status psk_db_locality(psk_db* db, uint32_t* slot_of, uint32_t* n_groups, uint32_t* is_identity) {
+    if (!db) { psk_set_error("db_locality: NULL database"); return PSK_EINVAL; }
+    PSK_LANE(lg, db->ctx);
+    std::unique_lock<std::shared_mutex> lk(db->rw);      // (computes the order if references were added since: exclusive, like the index builds)
+    PSK_TRY(ensure_locality(lg.lane, db, n_groups != nullptr));
+    const uint32_t n = (uint32_t)db->refs.size();
+    if (slot_of) for (uint32_t r = 0; r < n; r++) slot_of[r] = db->loc_identity ? r : db->slot_of[r];
+    if (n_groups) *n_groups = db->loc_groups;
+    if (is_identity) *is_identity = db->loc_identity ? 1u : 0u;
+    return PSK_OK;
+}
 
 psk_status psk_screen(psk_db* db, const psk_sketch* q, double screen_val, int rescue_small, uint8_t* pass, uint32_t* shared) {
     if (!db || !q || !pass) { psk_set_error("screen: NULL argument"); return PSK_EINVAL; }

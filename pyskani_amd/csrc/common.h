@@ -486,7 +486,7 @@ struct psk_db {
     bool desc_dirty = true;
     uint64_t desc_indexed = 0; uint32_t desc_n = 0;
     PoolScratch d_refdesc, d_canon;
-    std::vector<SketchDesc> h_refdesc;
+    std::vector<SketchDesc> h_refdesc, h_refdesc_slot;
     // database-wide seed index (seed_index.hip build_gsi): EVERY reference's seeds sorted by k-mer (stable: within a k-mer by reference, contig, position).
     // One lookup per query seed finds its matches in all references at once: the seed prefilter of a rescued contig in the one-launch-sequence
     // query, the join of batches of many small pairs (metagenome). gsi_val = ref << 48 | contig << 33 | pos << 1 | (fwd < rc); built once per
@@ -507,7 +507,23 @@ struct psk_db {
     uint64_t bsi_n = 0; int bsi_shift = 0; uint32_t bsi_nb1 = 0, bsi_blocks = 0;      // nb1 = bucket-table entries per block (2^bits + 1)
     // the one-launch-sequence query (small_query.hip): 1 = every device table it reads is up to date, 2 = this database cannot take it; reset when references are added
     std::atomic<int> small_state{0};
+    // the locality order (locality.hip): slot s of the seed indexes, the descriptor table of the many-query path and the columns of its pass matrix holds reference
+    // ref_of[s]; identity (empty vectors, no device copies: nothing translates) until computed and whenever the references' groups are contiguous already.
+    // 0 = stale (references were added), 1 = computed. Computed under the exclusive lock before any table that is laid out by it.
+    int loc_state = 0;
+    bool loc_identity = true, loc_groups_known = false;
+    uint32_t loc_groups = 0;
+    std::vector<uint32_t> ref_of, slot_of;
+    PoolScratch d_ref_of, d_slot_of, d_refdesc_slot;      // d_refdesc_slot: the descriptor table in slot order (d_refdesc stays in insertion order: the one-launch-sequence query reads it)
+    void stale() {      // references were added: every device table and the order go
+        tables_dirty = true; inv_dirty = true; desc_dirty = true; small_state = 0; gsi_key.release(); gsi_val.release(); gsi_bucket.release(); gsi_state = 0;
+        bsi_key.release(); bsi_val.release(); bsi_bucket.release(); bsi_base.release(); bsi_state = 0;
+        loc_state = 0;
+    }
 };
+
+// locality.hip: computes the order if it is stale; called with the database locked exclusively. want_groups: the count of groups too (psk_db_locality)
+psk_status ensure_locality(Lane* ctx, psk_db* db, bool want_groups = false);
 
 // learned-ANI regression model: flattened trees in HBM
 struct ModelNode { int32_t feature; float threshold; int32_t left, right; float value; int32_t missing, is_leaf, menu; };  // menu = psk_feature id of `feature`

@@ -172,6 +172,14 @@ psk_status refresh_ref_descs(Lane* ctx, psk_db* db) {
     for (uint32_t i = 0; i < n; i++) h[i] = make_desc(db->refs[i]);
     PSK_TRY(db->d_refdesc.reserve(ctx->dev, sizeof(SketchDesc) * (size_t)n + 256));
     PSK_HIP(hipMemcpyAsync(db->d_refdesc.p, h.data(), sizeof(SketchDesc) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    PSK_TRY(ensure_locality(ctx, db));
+    if (!db->loc_identity) {      // the many-query path's table: slot order
+        std::vector<SketchDesc>& hs = db->h_refdesc_slot;
+        hs.resize(n);
+        for (uint32_t s = 0; s < n; s++) hs[s] = h[db->ref_of[s]];
+        PSK_TRY(db->d_refdesc_slot.reserve(ctx->dev, sizeof(SketchDesc) * (size_t)n + 256));
+        PSK_HIP(hipMemcpyAsync(db->d_refdesc_slot.p, hs.data(), sizeof(SketchDesc) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    }
     db->desc_dirty = false; db->desc_indexed = indexed; db->desc_n = n;
     return PSK_OK;
 }
@@ -224,13 +232,14 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
     // queries per round (pass matrix <= 1 GiB). A round costs ~3.5 ms of host work with the GPU idle (its screen set-up, the shortlist, the last batch's hits):
     // 65 536 queries per round instead of 16 384 is 2 rounds instead of 7 for 100 000 contigs (metagenome step 420 -> 384 ms); PSK_ROUND_QUERIES overrides (tests, A/B)
     const uint32_t qb_env = sw.round_queries.get() ? (uint32_t)std::max(1, (int)sw.round_queries.num(0)) : 0u;
-    const uint32_t QB = std::max<uint32_t>(1, std::min<uint32_t>(qb_env ? qb_env : 65536u, (uint32_t)((1ull << 30) / n)));
+    uint32_t QB = std::max<uint32_t>(1, std::min<uint32_t>(qb_env ? qb_env : 65536u, (uint32_t)((1ull << 30) / n)));
     {
         const char* force = sw.screen.get();
         const bool want_inv = force ? !strcmp(force, "inv") : ((uint64_t)n * std::min(QB, n_queries) >= (1ull << 18));
-        if (db->tables_dirty || (want_inv && db->inv_dirty) || (db->has_dups && db->canon_dirty))
+        if (db->tables_dirty || (want_inv && db->inv_dirty) || (db->has_dups && db->canon_dirty) || db->loc_state == 0)
             PSK_TRY(exclusive([&]() -> psk_status {
                 PSK_TRY(upload_marker_table(ctx, db));
+                PSK_TRY(ensure_locality(ctx, db));
                 if (want_inv) PSK_TRY(build_inverted(ctx, db));
                 if (db->has_dups && db->canon_dirty) {
                     PSK_TRY(db->d_canon.reserve(ctx->dev, 4 * (size_t)n));
@@ -240,6 +249,13 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                 return PSK_OK;
             }));
     }
+    // The locality order (locality.hip): where it is not the identity, everything behind the screen - the pass matrix's columns, the references' descriptors, both seed
+    // indexes, the pairs and the hits' ref_index - is in SLOT order; the screen (marker table, inverted index, canon) stays in insertion order and its pass matrix is
+    // carried over by one gather, and the hits are mapped back and put in ascending reference order before they leave. The identity does none of it.
+    const bool loc = !db->loc_identity;
+    if (loc) QB = std::max<uint32_t>(1, std::min<uint32_t>(QB, (uint32_t)((1ull << 29) / n)));      // (two pass matrices per round)
+    auto ref_descs = [&]() { return (const SketchDesc*)(loc ? db->d_refdesc_slot.p : db->d_refdesc.p); };
+    const size_t all0 = all.n;
     std::vector<uint32_t> h_cnt; std::vector<uint8_t> h_flag;
     std::vector<SketchDesc> h_qd;
     int64_t h_qd_gsi_round = -1;      // the round (its first query) whose descriptors h_qd holds in the seed-index form (make_desc(.., true))
@@ -249,9 +265,10 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
     for (uint32_t b = 0; b < n_queries; b += QB) {
         const uint32_t m = std::min(QB, n_queries - b);
         // ---- screen: pass matrix on the device, counts + flags to the host
-        const size_t o_pass = 0, o_cnt = al256((size_t)m * n), o_flag = al256(o_cnt + 8 * (size_t)m), o_end = o_flag + n;      // (d_cnt: the queries' pass counts, then their counts of index blocks with a passing reference)
+        const size_t o_pass = 0, o_cnt = al256((size_t)m * n), o_flag = al256(o_cnt + 8 * (size_t)m), o_raw = al256(o_flag + n), o_end = o_raw + (loc ? (size_t)m * n : 0);      // (d_cnt: the queries' pass counts, then their counts of index blocks with a passing reference)
         PSK_TRY(ctx->q_i.reserve(o_end + 256));
         uint8_t* d_pass = (uint8_t*)ctx->q_i.p + o_pass; uint32_t* d_cnt = (uint32_t*)((char*)ctx->q_i.p + o_cnt); uint8_t* d_flag = (uint8_t*)ctx->q_i.p + o_flag;
+        uint8_t* d_raw = loc ? (uint8_t*)ctx->q_i.p + o_raw : d_pass;      // (the screen's pass matrix, columns in insertion order)
         // a single query (psk_query: one contig against the database) is as slow as its chain of waits: its k-mer index is launched here,
         // ahead of the screen, and not waited for - one host synchronisation fewer per call
         // (a database that has not been queried yet indexes its references and the query in ONE launch further down: the headline step)
@@ -259,8 +276,9 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
             queries[0]->params.k == db->params.k && queries[0]->params.c == db->params.c)
             PSK_TRY(ensure_index(ctx, queries, 1, true));
         ScreenStaging keep;
-        PSK_TRY(screen_many_device(ctx, db, queries + b, m, screen_val, !o->faster_small, d_pass, keep, sw));
-        if (db->has_dups) hipLaunchKernelGGL(pass_canon_kernel, dim3(m), dim3(256), 0, st, d_pass, n, (const uint32_t*)db->d_canon.p);
+        PSK_TRY(screen_many_device(ctx, db, queries + b, m, screen_val, !o->faster_small, d_raw, keep, sw));
+        if (db->has_dups) hipLaunchKernelGGL(pass_canon_kernel, dim3(m), dim3(256), 0, st, d_raw, n, (const uint32_t*)db->d_canon.p);
+        if (loc) pass_to_slots_launch(d_raw, d_pass, m, n, (const uint32_t*)db->d_ref_of.p, st);
         // ---- rescued short queries: exact anchor counts against every reference, pairs that cannot chain leave the pass matrix
         PoolScratch pf_buf;      // lives until the round's synchronisations are through, like the host arrays the copies read
         std::vector<uint32_t> rq, eoff, qn;
@@ -345,7 +363,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                 const uint32_t chunks = std::max<uint32_t>(1, std::min<uint32_t>(n, 4096 / slices));      // ~4 096 workgroups in all
                 const uint32_t rpc = (n + chunks - 1) / chunks;
                 hipLaunchKernelGGL(pref_count_kernel, dim3(slices, (n + rpc - 1) / rpc), dim3(PF_T), 0, st, (const uint32_t*)k1, (const uint32_t*)v1, (uint32_t)E, slice_shift,
-                                   (const SketchDesc*)db->d_refdesc.p, n, rpc, d_pcnt, d_ovf);
+                                   ref_descs(), n, rpc, d_pcnt, d_ovf);
                 hipLaunchKernelGGL(pref_apply_kernel, dim3((uint32_t)(((size_t)nr * n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_pcnt, (const uint32_t*)d_rq, nr, n, (const uint32_t*)d_ovf, d_pass);
             }
         }
@@ -374,7 +392,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
         }
         // ---- the references and queries about to be chained: validate, index, describe
         std::vector<const psk_sketch*> need;
-        for (uint32_t r = 0; r < n; r++) if (h_flag[r]) {
+        for (uint32_t r = 0; r < n; r++) if (h_flag[slot_at(db, r)]) {      // (h_flag is per slot; in reference order: the first reference that cannot be chained is the one named)
             const psk_sketch* rs = db->refs[r];
             if (!rs->has_seeds) { psk_set_error("reference %u ('%s') was sketched with seed=False; it cannot be chained", r, db->names[r].c_str()); return PSK_EINVAL; }
             need.push_back(rs);
@@ -538,6 +556,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                 memcpy(all.p + old + lo, pend_hits + lo, sizeof(H) * (hi - lo));
                 for (size_t i = lo; i < hi; i++) {
                     H& h = all.p[old + i];
+                    if (loc) h.ref_index = db->ref_of[h.ref_index];
                     const uint32_t lq = HitRec<H>::local_query(h);
                     if (shared) __atomic_fetch_add(&q_hits[lq], 1u, __ATOMIC_RELAXED); else q_hits[lq]++;      // (slices meet inside a query's hits)
                     HitRec<H>::finish(h, b + lq);
@@ -594,7 +613,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                 bool live[2] = {false, false};
                 Lane* lanes[2] = {ctx, lane2->lane};
                 PSK_HIP(hipStreamSynchronize(st));      // the round's tables (pass matrix, query descriptors) are complete before the other stream reads them
-                const SketchDesc* d_rd = (const SketchDesc*)db->d_refdesc.p;
+                const SketchDesc* d_rd = ref_descs();
                 auto exec = [&](Lane* ln, PipeJob* Jp) {
                     PipeJob& J = *Jp;
                     (void)hipSetDevice(ln->device);
@@ -690,7 +709,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                     if (nh) {
                         if (!all.reserve_for(nh)) { psk_set_error("out of host memory"); return PSK_ENOMEM; }
                         memcpy(all.p + all.n, J.hits.data(), sizeof(H) * nh);
-                        for (size_t i = 0; i < nh; i++) { H& h = all.p[all.n + i]; const uint32_t lq = HitRec<H>::local_query(h); q_hits[lq]++; HitRec<H>::finish(h, b + lq); }
+                        for (size_t i = 0; i < nh; i++) { H& h = all.p[all.n + i]; if (loc) h.ref_index = db->ref_of[h.ref_index]; const uint32_t lq = HitRec<H>::local_query(h); q_hits[lq]++; HitRec<H>::finish(h, b + lq); }
                         all.n += nh;
                     }
                     ctx->dev->w_pairs += J.pairs; ctx->dev->w_items += J.items; ctx->dev->w_anchors += J.anchors; ctx->dev->w_cands += J.cands; ctx->dev->w_rows += J.wrows;
@@ -797,7 +816,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                 if (lrc == PSK_ENOMEM && n_pairs > 1 && max_items > (1ull << 22)) { max_items >>= 2; continue; }
                 PSK_TRY(lrc);
                 PSK_HIP(hipMemcpyAsync(L.bq, bqs.data(), sizeof(BatchQ) * bqs.size(), hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(pair_build_rows_kernel, dim3((uint32_t)bqs.size()), dim3(256), 0, st, L.bq, d_pass, n, d_qd, (const SketchDesc*)db->d_refdesc.p,
+                hipLaunchKernelGGL(pair_build_rows_kernel, dim3((uint32_t)bqs.size()), dim3(256), 0, st, L.bq, d_pass, n, d_qd, ref_descs(),
                                    L.pairs, L.sbase, L.cbase, L.pair_qr, n_pairs, (uint32_t)items, (uint32_t)rows);
                 // a small batch: status and every record in one copy; a large one: the status alone is waited for, the selected hits then cross on the copy
                 // stream WHILE THE NEXT BATCH COMPUTES (600 MB per metagenome step: 15 ms of copies that kept the compute queues idle), out of one of two
@@ -822,7 +841,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                 for (int attempt = 0;; attempt++) {
                     struct timespec tb0{}, tb1{}, tb2{};
                     if (trace_batch) clock_gettime(CLOCK_MONOTONIC, &tb0);
-                    psk_status rrc = chain_run(ctx, L, n_pairs, (size_t)items, (size_t)rows, db->params, o, d_qd, (const SketchDesc*)db->d_refdesc.p, cap, wide, sw, round_probe && !round_gsi);
+                    psk_status rrc = chain_run(ctx, L, n_pairs, (size_t)items, (size_t)rows, db->params, o, d_qd, ref_descs(), cap, wide, sw, round_probe && !round_gsi);
                     if (trace_batch) clock_gettime(CLOCK_MONOTONIC, &tb1);
                     if (rrc == PSK_ENOMEM && n_pairs > 1 && max_items > (1ull << 22)) { (void)hipStreamSynchronize(st); ctx->huge_release(); too_big = true; break; }
                     PSK_TRY(rrc);
@@ -877,6 +896,12 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
         }
         PSK_TRY(consume());
         for (uint32_t i = 0; i < m; i++) offsets[b + i + 1] = offsets[b + i] + q_hits[i];
+        if (loc)      // a query's hits came in slot order: runs of ascending references, one per group - most queries have one group and are in order already
+            for (uint32_t i = 0; i < m; i++) {
+                H* h0 = all.p + all0 + offsets[b + i]; H* h1 = all.p + all0 + offsets[b + i + 1];
+                auto by_ref = [](const H& x, const H& y) { return x.ref_index < y.ref_index; };
+                if (!std::is_sorted(h0, h1, by_ref)) std::sort(h0, h1, by_ref);
+            }
     }
     return PSK_OK;
 }

@@ -53,7 +53,8 @@ struct SwitchVal {
     X(gsi_onepass, "PSK_GSI_ONEPASS") \
     X(pipeline, "PSK_PIPELINE") \
     X(screen_global, "PSK_SCREEN_GLOBAL") \
-    X(screen_wave, "PSK_SCREEN_WAVE")
+    X(screen_wave, "PSK_SCREEN_WAVE") \
+    X(locality, "PSK_LOCALITY")
 struct Switches {
 #define X(field, name) SwitchVal field;
     PSK_SWITCHES(X)
@@ -110,6 +111,11 @@ psk_status chain_batch(Lane* ctx, const HostPair* hp, uint32_t n_pairs, const ps
 // ---- query_many.hip
 uint64_t index_stamp(const psk_db* db);
 psk_status refresh_ref_descs(Lane* ctx, psk_db* db);
+
+// ---- locality.hip: the database's locality order (psk_db::ref_of / slot_of); ensure_locality (common.h) is called with the database locked exclusively
+static inline uint32_t ref_at(const psk_db* db, uint32_t slot) { return db->loc_identity ? slot : db->ref_of[slot]; }
+static inline uint32_t slot_at(const psk_db* db, uint32_t ref) { return db->loc_identity ? ref : db->slot_of[ref]; }
+void pass_to_slots_launch(const uint8_t* in, uint8_t* out, uint32_t n_queries, uint32_t n_refs, const uint32_t* ref_of, hipStream_t st);
 
 // ---- seed_index.hip: called with the database locked exclusively; leave gsi_state / bsi_state 1 (built) or 2 (this database cannot have one)
 psk_status build_gsi(Lane* ctx, psk_db* db);

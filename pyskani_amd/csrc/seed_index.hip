@@ -32,10 +32,11 @@ psk_status build_gsi(Lane* ctx, psk_db* db) {
     const uint32_t n = (uint32_t)db->refs.size();
     db->gsi_state = 2;
     if (off || n == 0 || n > 65536u || db->params.k > 16) return PSK_OK;
-    std::vector<GsiSeg> segs(n);
+    { const psk_status lrc = ensure_locality(ctx, db); if (lrc != PSK_OK) { db->gsi_state = 0; return lrc; } }
+    std::vector<GsiSeg> segs(n);      // one segment per SLOT of the locality order: the entries' reference field holds the slot
     uint64_t N = 0; uint32_t maxn = 0;
     for (uint32_t i = 0; i < n; i++) {
-        const psk_sketch* r = db->refs[i];
+        const psk_sketch* r = db->refs[ref_at(db, i)];
         if (!r->has_seeds || r->contig_len.size() > (1u << GSI_CONTIG_BITS) || r->params.k != db->params.k || r->params.c != db->params.c) return PSK_OK;
         const uint32_t ns = r->store ? (uint32_t)r->n_seeds : 0u;
         segs[i] = GsiSeg{ns ? r->store->seed_kmer + r->seed_off : nullptr, ns ? r->store->seed_pm + r->seed_off : nullptr, ns, (uint32_t)N};
@@ -95,7 +96,8 @@ psk_status build_bsi(Lane* ctx, psk_db* db) {
     const uint32_t n = (uint32_t)db->refs.size();
     db->bsi_state = 2;
     if (off || n == 0 || db->params.k > 16) return PSK_OK;
-    // one segment per reference, offsets WITHIN its block; the blocks' own offsets are 64-bit (no bound on the references or the seeds of the database but memory)
+    { const psk_status lrc = ensure_locality(ctx, db); if (lrc != PSK_OK) { db->bsi_state = 0; return lrc; } }
+    // one segment per slot of the locality order (a block = 2^BSI_BLOG consecutive slots), offsets WITHIN its block; the blocks' own offsets are 64-bit (no bound on the references or the seeds of the database but memory)
     const uint32_t n_blocks = (n + (1u << BSI_BLOG) - 1) >> BSI_BLOG;
     std::vector<GsiSeg> segs(n);
     std::vector<uint64_t> base(n_blocks + 1, 0);
@@ -104,7 +106,7 @@ psk_status build_bsi(Lane* ctx, psk_db* db) {
         const uint32_t r0 = b << BSI_BLOG, r1 = std::min<uint32_t>(n, (b + 1) << BSI_BLOG);
         uint64_t in_block = 0;
         for (uint32_t i = r0; i < r1; i++) {
-            const psk_sketch* r = db->refs[i];
+            const psk_sketch* r = db->refs[ref_at(db, i)];
             if (!r->has_seeds || r->contig_len.size() > (1u << GSI_CONTIG_BITS) || r->params.k != db->params.k || r->params.c != db->params.c) return PSK_OK;
             const uint32_t ns = r->store ? (uint32_t)r->n_seeds : 0u;
             if (in_block + ns >= 0x7FFFFF00ull) return PSK_OK;      // (a block is one radix sort: 256 references of more than 8 M seeds each - 1 Gb at c = 125 - have none)

@@ -35,6 +35,7 @@ struct SqScreenArgs {
     uint32_t* shortlist;
     // database-wide seed index (null: none) and the query's seed k-mers: the seed prefilter of a rescued contig
     const uint32_t* gsi_key; const unsigned long long* gsi_val; const uint32_t* gsi_bucket; int gsi_shift; const uint32_t* q_kmer;
+    const uint32_t* gsi_ref_of;      // the index's reference field is a slot of the database's locality order: slot -> reference (null: the identity)
 };
 
 // exclusive scan over the workgroup's threads (blockDim = SQ_SCREEN_T), total to every thread
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(SQ_SCREEN_T) void sq_screen_kernel(SqScreenArgs A) 
             for (int u = 0; u < U; u++) { lo[u] = 0; hi[u] = 0; if (i0 + u < nq) { const uint32_t b = km[u] >> A.gsi_shift; lo[u] = A.gsi_bucket[b]; hi[u] = A.gsi_bucket[b + 1]; } }
 #pragma unroll
             for (int u = 0; u < U; u++)
-                for (uint32_t x = lo[u] + lane; x < hi[u]; x += 64u) if (A.gsi_key[x] == km[u]) atomicAdd(&s_count[(uint32_t)(A.gsi_val[x] >> 48)], 2u);      // (bit 0: the pass flag)
+                for (uint32_t x = lo[u] + lane; x < hi[u]; x += 64u) if (A.gsi_key[x] == km[u]) { const uint32_t sl = (uint32_t)(A.gsi_val[x] >> 48); atomicAdd(&s_count[A.gsi_ref_of ? A.gsi_ref_of[sl] : sl], 2u); }      // (bit 0: the pass flag)
         }
         __syncthreads();
         for (uint32_t r = tid; r < A.n_refs; r += SQ_SCREEN_T) { const uint32_t v = s_count[r]; s_count[r] = (v & 1u) && (v >> 1) >= MIN_ANCHORS ? 1u : 0u; }
@@ -741,7 +742,7 @@ psk_status query_host_small(Lane* ctx, psk_db* db, const uint8_t* const* contigs
     SA.canon = db->has_dups ? (const uint32_t*)db->d_canon.p : nullptr;
     SA.shortlist = (uint32_t*)(D + w_short);
     static const bool pf_off = env_val("PSK_SQ_PREFILTER").off();      // tests, A/B
-    if (db->gsi_state == 1 && !pf_off) { SA.gsi_key = (const uint32_t*)db->gsi_key.p; SA.gsi_val = (const unsigned long long*)db->gsi_val.p; SA.gsi_bucket = (const uint32_t*)db->gsi_bucket.p; SA.gsi_shift = db->gsi_shift; }
+    if (db->gsi_state == 1 && !pf_off) { SA.gsi_key = (const uint32_t*)db->gsi_key.p; SA.gsi_val = (const unsigned long long*)db->gsi_val.p; SA.gsi_bucket = (const uint32_t*)db->gsi_bucket.p; SA.gsi_shift = db->gsi_shift; SA.gsi_ref_of = db->loc_identity ? nullptr : (const uint32_t*)db->d_ref_of.p; }
     SA.q_kmer = S.seed_kmer;
     static std::once_flag lds_once;
     static hipError_t lds_rc = hipSuccess;

@@ -773,6 +773,17 @@ class Database:
         with Database._Borrow(self, False):
             return self._query(name, contigs, seed, learned_ani, median, robust, cutoff, faster_small)
 
+    def locality(self):
+        """The database's internal order of its references, in which relatives are neighbours (the seed indexes are laid out by it; names, indices and
+        hits stay in insertion order). Returns `(slot_of, n_groups)`: a numpy uint32 array with the position of every reference, and the number of
+        groups of relatives found. Computed on the GPU when references were added since the last time."""
+        with Database._Borrow(self, False):
+            n = self._lib.psk_db_size(self._h)
+            slot_of = np.empty(n, dtype=np.uint32)
+            groups = C.c_uint32(0)
+            _capi.check(self._lib.psk_db_locality(self._h, slot_of.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(groups), None))
+            return slot_of, int(groups.value)
+
     def _query(self, name, contigs, seed, learned_ani, median, robust, cutoff, faster_small):
         opts = self._opts(learned_ani, median, robust, cutoff, faster_small)
         if self._n_lazy:

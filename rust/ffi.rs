@@ -45,7 +45,7 @@ extern "C" {
     // errors, version, memory
     pub fn psk_last_error() -> *const c_char;
     pub fn psk_version() -> *const c_char;
-    pub fn psk_abi_version() -> c_int;      // compare with PSK_ABI_VERSION (5) before anything else is called
+    pub fn psk_abi_version() -> c_int;      // compare with PSK_ABI_VERSION (6) before anything else is called
     pub fn psk_free(p: *mut c_void);
     // context (one per GPU)
     pub fn psk_ctx_create(device: c_int, out: *mut *mut PskCtx) -> c_int;
@@ -124,6 +124,8 @@ extern "C" {
                           hits: *mut *mut PskHit, offsets: *mut u64) -> c_int;
     pub fn psk_query_many_min(db: *mut PskDb, qs: *const *const PskSketch, n: u32, o: *const PskQueryOpts,
                               hits: *mut *mut PskHitMin, offsets: *mut u64) -> c_int;
+    // the locality order of the references (slot_of: psk_db_size entries or null)
+    pub fn psk_db_locality(db: *mut PskDb, slot_of: *mut u32, n_groups: *mut u32, is_identity: *mut u32) -> c_int;
     // the two halves of `query`, for a disk-backed Database (markers resident, sketches loaded per query)
     pub fn psk_screen(db: *mut PskDb, q: *const PskSketch, screen_val: f64, rescue_small: c_int,
                       pass: *mut u8, shared: *mut u32) -> c_int;
