@@ -102,9 +102,9 @@ const char* psk_last_error(void);
 const char* psk_version(void);
 /* The C-ABI's revision: raised whenever an entry point's parameters or a structure's layout change (4: psk_sketch_unpack takes the extent of its source buffer as third
  * argument; 5: psk_hit_min / psk_query_many_min / psk_gather_hits_min / psk_ctx_join_work added;
- * 6: psk_db_locality added). A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
+ * 6: psk_db_locality added; 7: psk_ctx_rerun_stats added). A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
  * written against before it calls anything else: an argument list that moved is a memory error, not a link error. */
-#define PSK_ABI_VERSION 6
+#define PSK_ABI_VERSION 7
 int psk_abi_version(void);
 /* Releases an array the library returned (hit lists, gathered lists). Never release such an array with free(): large hit arrays are
  * huge-page blocks the library keeps one of for its next call ($PSK_HIT_CACHE=0: returned to the system at once). */
@@ -131,6 +131,11 @@ psk_status psk_ctx_join_work(psk_ctx* ctx, uint64_t* lookups, uint64_t* visited,
 /* Measurement: psk_query_host calls since the context was created that ran as one launch sequence (`taken`), that exceeded one of its
  * capacities and were rerun on the general path (`rerun`), and that went to the general path at once (`general`, which includes `rerun`). */
 psk_status psk_ctx_small_query_stats(psk_ctx* ctx, uint64_t* taken, uint64_t* rerun, uint64_t* general);
+/* Measurement: batches of the chain stage that were sent round again since the last reset, by cause. `cap`: the anchor total exceeded the optimistically sized
+ * anchor arrays; `wide`: a seed with 255 or more matches (or a contig number of 2^23 or more) asked for the wide join format; `onepass`: a pair outgrew its room
+ * in the one-walk index join and the batch took the count pass; `refit`: a batch of the two-lane pipeline was handed back to the one-chain loop (a wide request,
+ * too many anchors for one launch, or no memory). Read-only: no decision depends on them. Any pointer may be NULL. */
+psk_status psk_ctx_rerun_stats(psk_ctx* ctx, uint64_t* cap, uint64_t* wide, uint64_t* onepass, uint64_t* refit, int reset);
 /* Host-side 2-bit packing of the ingest pipeline (csrc/pack_host.cpp), exposed for tests: n ASCII bases -> ceil(n / 16) words, the first base in a
  * word's highest two bits; A 0, C 1, G 2, T 3, case-insensitive, every other byte 0 (the codes of the sketch kernels). mode 0: the best
  * implementation the CPU has (AVX-512BW), 1: the scalar one. */

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("PSK_LIB_PATH") or os.path.join(_HERE, "libpyskani_amd
 
 PSK_OK, PSK_EINVAL, PSK_ENOMEM, PSK_EHIP, PSK_ENOMODEL, PSK_EKEY, PSK_ELIMIT, PSK_ERCCL = range(8)
 COMM_ID_BYTES = 128
-ABI_VERSION = 6      # PSK_ABI_VERSION of include/pyskani_amd.h this binding was written against
+ABI_VERSION = 7      # PSK_ABI_VERSION of include/pyskani_amd.h this binding was written against
 
 
 class Params(C.Structure):
@@ -54,7 +54,7 @@ class Seed(C.Structure):
 # every symbol include/pyskani_amd.h declares
 SYMBOLS = [
     "psk_last_error", "psk_version", "psk_abi_version", "psk_free", "psk_ctx_create", "psk_ctx_destroy",
-    "psk_ctx_synchronize", "psk_pack2bit_host", "psk_ctx_small_query_stats", "psk_ctx_set_timing", "psk_ctx_timing", "psk_db_add_batch", "psk_device_alloc", "psk_device_free", "psk_memcpy_h2d",
+    "psk_ctx_synchronize", "psk_pack2bit_host", "psk_ctx_small_query_stats", "psk_ctx_rerun_stats", "psk_ctx_set_timing", "psk_ctx_timing", "psk_db_add_batch", "psk_device_alloc", "psk_device_free", "psk_memcpy_h2d",
     "psk_sketch_host", "psk_sketch_many_host", "psk_sketch_batch_device", "psk_sketch_free", "psk_sketch_free_many", "psk_sketch_info",
     "psk_sketch_export", "psk_sketch_contig_lens", "psk_sketch_import", "psk_db_create", "psk_db_destroy", "psk_db_add", "psk_db_size",
     "psk_db_name", "psk_db_sketch", "psk_db_locality", "psk_screen", "psk_chain", "psk_query", "psk_query_host", "psk_query_many", "psk_query_many_min", "psk_gather_hits_min",
@@ -88,6 +88,7 @@ def load():
     lib.psk_ctx_destroy.restype = None
     lib.psk_ctx_synchronize.argtypes = [vp]
     lib.psk_ctx_small_query_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    lib.psk_ctx_rerun_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.c_int]
     lib.psk_pack2bit_host.argtypes = [vp, u64, vp, C.c_int]
     lib.psk_pack2bit_host.restype = None
     lib.psk_ctx_set_timing.argtypes = [vp, C.c_int]

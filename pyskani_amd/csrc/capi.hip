@@ -239,6 +239,15 @@ psk_status psk_ctx_small_query_stats(psk_ctx* c, uint64_t* taken, uint64_t* reru
     if (general) *general = c->sq_general.load();
     return PSK_OK;
 }
+psk_status psk_ctx_rerun_stats(psk_ctx* c, uint64_t* cap, uint64_t* wide, uint64_t* onepass, uint64_t* refit, int reset) {
+    if (!c) { psk_set_error("NULL ctx"); return PSK_EINVAL; }
+    if (cap) *cap = c->rr_cap.load();
+    if (wide) *wide = c->rr_wide.load();
+    if (onepass) *onepass = c->rr_onepass.load();
+    if (refit) *refit = c->rr_refit.load();
+    if (reset) { c->rr_cap = 0; c->rr_wide = 0; c->rr_onepass = 0; c->rr_refit = 0; }
+    return PSK_OK;
+}
 psk_status psk_device_alloc(psk_ctx* c, size_t bytes, void** dptr) {
     if (!c || !dptr) { psk_set_error("device_alloc: NULL argument"); return PSK_EINVAL; }
     PSK_HIP(hipSetDevice(c->device));

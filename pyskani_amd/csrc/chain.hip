@@ -624,8 +624,9 @@ psk_status chain_batch(Lane* ctx, const HostPair* hp, uint32_t n_pairs, const ps
         PSK_HIP(hipMemcpyAsync(T, L.misc, 256 + sizeof(psk_hit) * n_pairs, hipMemcpyDeviceToHost, st));      // status words, anchor total and the hits behind them: one copy (ChainTail mirrors misc[0..17])
         PSK_HIP(hipStreamSynchronize(st));      // the ONE synchronisation of a launch sequence (also keeps the host staging above alive)
         ctx->huge_release();
-        bool retry;
+        bool retry; const bool was_wide = wide;
         PSK_TRY(chain_check(*T, n_pairs, &cap, &wide, &retry));
+        count_rerun(ctx->dev, was_wide, wide, retry);
         if (!retry) { ctx->dev->w_pairs += n_pairs; ctx->dev->w_items += items; ctx->dev->w_anchors += T->total64; ctx->dev->w_cands += T->cands; ctx->dev->w_rows += T->rows; break; }
         if (attempt >= 3) { psk_set_error("internal: anchor capacity did not converge"); return PSK_EHIP; }
     }

@@ -108,6 +108,9 @@ struct psk_ctx {
     std::atomic<uint64_t> w_lookups{0}, w_visited{0}, w_cands{0}, w_rows{0};
     // psk_query_host calls that ran as one launch sequence / were rerun on the general path because a capacity was exceeded / never qualified (psk_ctx_small_query_stats)
     std::atomic<uint64_t> sq_taken{0}, sq_rerun{0}, sq_general{0};
+    // batches of the chain stage sent round again, by cause: anchor capacity / wide join format / the index join's count pass / a pipeline batch handed back to the
+    // one-chain loop (psk_ctx_rerun_stats; counted where the host decides, read by tests - no decision reads them)
+    std::atomic<uint64_t> rr_cap{0}, rr_wide{0}, rr_onepass{0}, rr_refit{0};
     // lanes: created on demand, at most max_lanes; a call takes a free one (LaneGuard) and gives it back
     std::mutex lanes_mu;
     std::condition_variable lanes_cv;

@@ -624,7 +624,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                         const uint32_t n_pairs = (uint32_t)J.pairs;
                         ChainBufs L;
                         psk_status lrc = chain_layout(ln, n_pairs, (size_t)J.items, (size_t)J.rows, J.bqs.size(), &L);
-                        if (lrc == PSK_ENOMEM) { J.refit = true; return PSK_OK; }
+                        if (lrc == PSK_ENOMEM) { J.refit = true; ctx->dev->rr_refit++; return PSK_OK; }
                         PSK_TRY(lrc);
                         L.rows_pair_max = (uint32_t)std::min<uint64_t>(J.rows_pair_max, 0xFFFFFFFFu);
                         L.g_key = (const uint32_t*)db->bsi_key.p; L.g_val = (const unsigned long long*)db->bsi_val.p; L.g_bucket = (const uint32_t*)db->bsi_bucket.p; L.g_shift = db->bsi_shift; L.g_nb1 = db->bsi_nb1; L.g_blocks = db->bsi_blocks; L.g_base = (const unsigned long long*)db->bsi_base.p;
@@ -640,7 +640,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                         const size_t o_tab = 0, o_eb = al256(o_tab + 8 * J.tab.size()), o_cnt = al256(o_eb + 8 * J.ebase.size()), o_rec = al256(o_cnt + 4 * (size_t)n_rec),
                                      o_bm = al256(o_rec + 16 * (size_t)n_rec), o_un = al256(o_bm + 4 * (size_t)GSL_WORDS * (size_t)n_rec), o_endj = o_un + 4 * (size_t)GSL_WORDS * (size_t)n_sl;
                         lrc = ln->q_j.reserve(o_endj + 256);
-                        if (lrc == PSK_ENOMEM) { J.refit = true; return PSK_OK; }
+                        if (lrc == PSK_ENOMEM) { J.refit = true; ctx->dev->rr_refit++; return PSK_OK; }
                         PSK_TRY(lrc);
                         char* Jb = (char*)ln->q_j.p;
                         PSK_HIP(hipMemcpyAsync(Jb + o_tab, J.tab.data(), 8 * J.tab.size(), hipMemcpyHostToDevice, s2));
@@ -651,7 +651,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                         hipLaunchKernelGGL(pair_build_rows_kernel, dim3((uint32_t)J.bqs.size()), dim3(256), 0, s2, L.bq, d_pass, n, d_qd, d_rd, L.pairs, L.sbase, L.cbase, L.pair_qr, n_pairs, (uint32_t)J.items, (uint32_t)J.rows);
                         const bool host_filter = n_pairs <= 4096;
                         H* d_sel = nullptr;
-                        if (!host_filter) { lrc = ln->q_sel.reserve(al256(sizeof(H) * (size_t)n_pairs + 256)); if (lrc == PSK_ENOMEM) { J.refit = true; return PSK_OK; } PSK_TRY(lrc); d_sel = (H*)ln->q_sel.p; }
+                        if (!host_filter) { lrc = ln->q_sel.reserve(al256(sizeof(H) * (size_t)n_pairs + 256)); if (lrc == PSK_ENOMEM) { J.refit = true; ctx->dev->rr_refit++; return PSK_OK; } PSK_TRY(lrc); d_sel = (H*)ln->q_sel.p; }
                         void* hp = nullptr;
                         PSK_TRY(ln->pinned(al256(sizeof(psk_hit) * (size_t)n_pairs + 512), &hp));
                         ChainTail* T = (ChainTail*)hp; H* h_sel = (H*)((char*)hp + 256);
@@ -660,7 +660,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                         bool wide = sw.join_wide();
                         for (int attempt = 0;; attempt++) {
                             psk_status rrc = chain_run(ln, L, n_pairs, (size_t)J.items, (size_t)J.rows, db->params, o, d_qd, d_rd, cap, wide, sw, false);
-                            if (rrc == PSK_ENOMEM) { (void)hipStreamSynchronize(s2); J.refit = true; return PSK_OK; }
+                            if (rrc == PSK_ENOMEM) { (void)hipStreamSynchronize(s2); J.refit = true; ctx->dev->rr_refit++; return PSK_OK; }
                             PSK_TRY(rrc);
                             if (!host_filter) {
                                 size_t tmp3 = 0;
@@ -673,7 +673,8 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                             PSK_HIP(hipStreamSynchronize(s2));
                             bool retry, was_wide = wide;
                             psk_status rc = chain_check(*T, n_pairs, &cap, &wide, &retry);
-                            if ((rc == PSK_ELIMIT && n_pairs > 1) || wide != was_wide) { J.refit = true; return PSK_OK; }      // (the one-chain loop knows what to do with these)
+                            count_rerun(ctx->dev, was_wide, wide, retry);
+                            if ((rc == PSK_ELIMIT && n_pairs > 1) || wide != was_wide) { J.refit = true; ctx->dev->rr_refit++; return PSK_OK; }      // (the one-chain loop knows what to do with these)
                             PSK_TRY(rc);
                             if (!retry) break;
                             if (attempt >= 3) { psk_set_error("internal: anchor capacity did not converge"); return PSK_EHIP; }
@@ -860,16 +861,18 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                         clock_gettime(CLOCK_MONOTONIC, &tb2);
                         static struct timespec last{};
                         const double gap = last.tv_sec ? (tb0.tv_sec - last.tv_sec) * 1e3 + (tb0.tv_nsec - last.tv_nsec) / 1e6 : 0.0;
-                        fprintf(stderr, "[psk batch] pairs %u items %llu attempt %d: since last %.1f ms, launch %.1f ms, wait %.1f ms\n", n_pairs, (unsigned long long)items, attempt, gap,
-                                (tb1.tv_sec - tb0.tv_sec) * 1e3 + (tb1.tv_nsec - tb0.tv_nsec) / 1e6, (tb2.tv_sec - tb1.tv_sec) * 1e3 + (tb2.tv_nsec - tb1.tv_nsec) / 1e6);
+                        fprintf(stderr, "[psk batch] pairs %u items %llu attempt %d: since last %.1f ms, launch %.1f ms, wait %.1f ms; anchors %llu of %llu, status %x, wide %u -> %u\n", n_pairs, (unsigned long long)items, attempt, gap,
+                                (tb1.tv_sec - tb0.tv_sec) * 1e3 + (tb1.tv_nsec - tb0.tv_nsec) / 1e6, (tb2.tv_sec - tb1.tv_sec) * 1e3 + (tb2.tv_nsec - tb1.tv_nsec) / 1e6,
+                                (unsigned long long)T->total64, (unsigned long long)cap, T->misc[0], wide ? 1u : 0u, T->misc[5]);      // (status bit 2: an emit kernel met its capacity guard; bit 4: a pair outgrew its one-walk room)
                         last = tb2;
                     }
                     ctx->huge_release();
-                    bool retry;
+                    bool retry; const bool was_wide = wide;
                     psk_status rc = chain_check(*T, n_pairs, &cap, &wide, &retry);
+                    count_rerun(ctx->dev, was_wide, wide, retry);
                     if (rc == PSK_ELIMIT && n_pairs > 1) { too_big = true; break; }
                     PSK_TRY(rc);
-                    if (!retry && L.gsi_onepass && (T->misc[0] & 4u)) { L.gsi_onepass = false; retry = true; }      // a pair with more anchors than query seeds: with the count pass
+                    if (!retry && L.gsi_onepass && (T->misc[0] & 4u)) { L.gsi_onepass = false; retry = true; ctx->dev->rr_onepass++; }      // a pair with more anchors than query seeds: with the count pass
                     if (!retry) {
                         ctx->dev->w_pairs += n_pairs; ctx->dev->w_items += items; ctx->dev->w_anchors += T->total64; ctx->dev->w_cands += T->cands; ctx->dev->w_rows += T->rows;
                         if (round_gsi) { uint64_t lk = 0; for (const BatchQ& e : bqs) lk += h_qd[e.q].n; ctx->dev->w_lookups += lk; ctx->dev->w_visited += T->visited; }

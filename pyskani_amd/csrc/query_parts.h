@@ -105,6 +105,8 @@ uint64_t anchor_cap_for(Lane* ctx, size_t n_items, bool sparse = false, bool gb_
 // outcome of a launch sequence, read back with the hits
 struct ChainTail { uint32_t misc[16]; unsigned long long total64, visited, cands, rows; };      // (misc[16..23]: the anchor total; index entries the join visited; with the timers on, candidates and live chunk rows)
 psk_status chain_check(const ChainTail& T, uint32_t n_pairs, uint64_t* cap, bool* wide, bool* retry);
+// psk_ctx_rerun_stats: what chain_check asked for after an attempt in the format `was_wide` (counted, never read back)
+static inline void count_rerun(psk_ctx* dev, bool was_wide, bool wide, bool retry) { if (wide && !was_wide) dev->rr_wide++; else if (retry) dev->rr_cap++; }
 struct HostPair { const psk_sketch* r; const psk_sketch* q; };
 psk_status chain_batch(Lane* ctx, const HostPair* hp, uint32_t n_pairs, const psk_query_opts* o, psk_hit* out, const Switches& sw);
 

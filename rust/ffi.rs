@@ -45,7 +45,7 @@ extern "C" {
     // errors, version, memory
     pub fn psk_last_error() -> *const c_char;
     pub fn psk_version() -> *const c_char;
-    pub fn psk_abi_version() -> c_int;      // compare with PSK_ABI_VERSION (6) before anything else is called
+    pub fn psk_abi_version() -> c_int;      // compare with PSK_ABI_VERSION (7) before anything else is called
     pub fn psk_free(p: *mut c_void);
     // context (one per GPU)
     pub fn psk_ctx_create(device: c_int, out: *mut *mut PskCtx) -> c_int;
@@ -104,6 +104,7 @@ extern "C" {
     pub fn psk_model_predict(m: *const PskModel, rows: *const f32, n_rows: u32, out: *mut f32) -> c_int;
     // database: markers.push + sketches.store (lib.rs:501-508)
     pub fn psk_ctx_small_query_stats(ctx: *mut PskCtx, taken: *mut u64, rerun: *mut u64, general: *mut u64) -> c_int;
+    pub fn psk_ctx_rerun_stats(ctx: *mut PskCtx, cap: *mut u64, wide: *mut u64, onepass: *mut u64, refit: *mut u64, reset: c_int) -> c_int;
     pub fn psk_pack2bit_host(src: *const u8, n: u64, dst: *mut u32, mode: c_int);
     pub fn psk_db_create(ctx: *mut PskCtx, p: *const PskParams, out: *mut *mut PskDb) -> c_int;
     pub fn psk_db_destroy(db: *mut PskDb);

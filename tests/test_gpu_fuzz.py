@@ -161,7 +161,12 @@ def test_index_join_reruns_with_its_count_pass_when_a_reference_repeats_the_quer
         db.sketch(n, sq)
     osk = [(n, oracle.Sketch([sq], c=30, marker_c=200)) for n, sq in refs]
     queries = [("unit", unit), ("unit_mut", mutate(rng, unit, 0.03)), ("flank", a[15000:27000]), ("two", unit * 2)]
+    import ctypes as C
+    reruns = [C.c_uint64() for _ in range(4)]      # (cap, wide, onepass, refit)
+    assert db._lib.psk_ctx_rerun_stats(db._ctx._h, None, None, None, None, 1) == 0
     got_all = db.query_many(queries, learned_ani=False)
+    assert db._lib.psk_ctx_rerun_stats(db._ctx._h, *[C.byref(x) for x in reruns], 0) == 0
+    assert reruns[2].value == (1 if onepass == "1" else 0), [x.value for x in reruns]      # the rerun took place (and only where the single walk was tried)
     for (qn, qs), got in zip(queries, got_all):
         want = {n: r for n, r in oracle.query(osk, oracle.Sketch([qs], c=30, marker_c=200))}
         g = {h.reference_name: h for h in got}

@@ -91,9 +91,9 @@ def test_header_binding_and_null_database():
     from pyskani_amd import _capi
     header = open(os.path.join(ROOT, "include", "pyskani_amd.h")).read()
     assert re.search(r"psk_status psk_db_locality\(psk_db\* db, uint32_t\* slot_of, uint32_t\* n_groups, uint32_t\* is_identity\);", header)
-    assert int(re.search(r"#define PSK_ABI_VERSION (\d+)", header).group(1)) == 6 == _capi.ABI_VERSION
+    assert int(re.search(r"#define PSK_ABI_VERSION (\d+)", header).group(1)) == 7 == _capi.ABI_VERSION
     lib = _capi.load()
-    assert lib.psk_abi_version() == 6
+    assert lib.psk_abi_version() == 7
     g, ident = C.c_uint32(7), C.c_uint32(7)
     assert lib.psk_db_locality(None, None, C.byref(g), C.byref(ident)) == _capi.PSK_EINVAL      # (before any lane or device is touched)
     assert (g.value, ident.value) == (7, 7)
