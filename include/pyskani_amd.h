@@ -102,7 +102,8 @@ const char* psk_last_error(void);
 const char* psk_version(void);
 /* The C-ABI's revision: raised whenever an entry point's parameters or a structure's layout change (4: psk_sketch_unpack takes the extent of its source buffer as third
  * argument; 5: psk_hit_min / psk_query_many_min / psk_gather_hits_min / psk_ctx_join_work added;
- * 6: psk_db_locality added; 7: psk_ctx_rerun_stats added). A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
+ * 6: psk_db_locality added; 7: psk_ctx_rerun_stats added). psk_query_many_tri and psk_query_many_tri_min came after 7 WITHOUT raising it: no existing argument
+ * list or structure moved, and a binding that wants them detects them by their presence (dlsym). A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
  * written against before it calls anything else: an argument list that moved is a memory error, not a link error. */
 #define PSK_ABI_VERSION 7
 int psk_abi_version(void);
@@ -308,6 +309,18 @@ psk_status psk_query_many(psk_db* db, const psk_sketch* const* queries, uint32_t
  * psk_hit stay on the device (what a parity test reads through psk_query_many); a metagenome step's 9.5 M hits are 190 MB instead of 763 MB over PCIe. */
 psk_status psk_query_many_min(psk_db* db, const psk_sketch* const* queries, uint32_t n_queries,
                               const psk_query_opts* opts, psk_hit_min** hits, uint64_t* offsets);
+
+/* Triangle mode of the two calls above: one signed 64-bit key per query and one reference base for the database. The pair (query i, reference r - insertion index)
+ * is chained iff query_key[i] < 0 or ref_base + r > query_key[i]; a negative key leaves that query as psk_query_many treats it. A database's own triangle - every
+ * unordered pair once, no genome against itself, what skani's `triangle` reports - is queries = its sketches in insertion order, query_key[i] = i, ref_base = 0:
+ * genome i is the query of every pair (i, j) with j > i. A sharded job passes the queries' GLOBAL indices and its shard's first global index. The mask is laid over
+ * the screen's pass matrix on the device (after the duplicate-name rule), so the pairs it removes are never chained, and a hit that remains is the very record of
+ * the unmasked call: same order (ascending query, then ref_index), offsets of n_queries + 1 entries. query_key == NULL with n_queries > 0: PSK_EINVAL;
+ * ref_base + the database's size beyond 2^63: PSK_ELIMIT. */
+psk_status psk_query_many_tri(psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const int64_t* query_key, uint64_t ref_base,
+                              const psk_query_opts* opts, psk_hit** hits, uint64_t* offsets);
+psk_status psk_query_many_tri_min(psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const int64_t* query_key, uint64_t ref_base,
+                                  const psk_query_opts* opts, psk_hit_min** hits, uint64_t* offsets);
 
 #ifdef __cplusplus
 }

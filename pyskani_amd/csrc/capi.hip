@@ -569,6 +569,39 @@ psk_status psk_query_many_min(psk_db* db, const psk_sketch* const* queries, uint
     return PSK_OK;
 }
 
+/* Triangle mode: psk_query_many / psk_query_many_min where the pair (query i, reference r) is chained iff query_key[i] < 0 or ref_base + r > query_key[i]
+ * (the mask is laid over the screen's pass matrix on the device: the pairs it removes never reach the chain stage). */
+static psk_status tri_args(const psk_db* db, const void* queries, uint32_t n_queries, const int64_t* query_key, uint64_t ref_base, const void* o, const void* hits, const void* offsets, const char* who) {
+    if (!db || (!queries && n_queries) || !o || !hits || !offsets) { psk_set_error("%s: NULL argument", who); return PSK_EINVAL; }
+    if (!query_key && n_queries) { psk_set_error("%s: NULL query_key", who); return PSK_EINVAL; }
+    if (ref_base > (1ull << 63) || ref_base + psk_db_size(db) > (1ull << 63)) { psk_set_error("%s: ref_base %llu + the database's size exceeds 2^63 (keys are signed 64-bit)", who, (unsigned long long)ref_base); return PSK_ELIMIT; }
+    return PSK_OK;
+}
+
+psk_status psk_query_many_tri(psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const int64_t* query_key, uint64_t ref_base,
+                              const psk_query_opts* o, psk_hit** hits, uint64_t* offsets) {
+    PSK_TRY(tri_args(db, queries, n_queries, query_key, ref_base, o, hits, offsets, "query_many_tri"));
+    *hits = nullptr;
+    offsets[0] = 0;
+    PSK_LANE(lg, db->ctx);
+    HitList all;
+    PSK_TRY(query_many_impl(lg.lane, db, queries, n_queries, o, all, offsets, n_queries ? query_key : nullptr, ref_base));
+    return hits_out(all, hits);
+}
+
+psk_status psk_query_many_tri_min(psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const int64_t* query_key, uint64_t ref_base,
+                                  const psk_query_opts* o, psk_hit_min** hits, uint64_t* offsets) {
+    PSK_TRY(tri_args(db, queries, n_queries, query_key, ref_base, o, hits, offsets, "query_many_tri_min"));
+    *hits = nullptr;
+    offsets[0] = 0;
+    PSK_LANE(lg, db->ctx);
+    HitListMin all;
+    PSK_TRY(query_many_min_impl(lg.lane, db, queries, n_queries, o, all, offsets, n_queries ? query_key : nullptr, ref_base));
+    if (!all.p) { all.p = (psk_hit_min*)malloc(sizeof(psk_hit_min)); if (!all.p) { psk_set_error("out of host memory"); return PSK_ENOMEM; } }      // no hit: still a pointer psk_free takes
+    *hits = all.release();
+    return PSK_OK;
+}
+
 }  // extern "C"
 
 

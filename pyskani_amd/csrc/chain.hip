@@ -87,6 +87,22 @@ __global__ __launch_bounds__(256) void pass_canon_kernel(uint8_t* __restrict__ p
     uint8_t* row = pass + (size_t)blockIdx.x * n_refs;
     for (uint32_t r = threadIdx.x; r < n_refs; r += blockDim.x) if (row[r] && canon[r] != r) { row[canon[r]] = 1; row[r] = 0; }   // canon[r] > r and canon[canon[r]] == canon[r]
 }
+// Triangle mode (psk_query_many_tri): the pair (row's query, reference r) stays iff key < 0 or ref_base + r > key, so a row loses its prefix [0, min(n_refs, key - ref_base + 1)).
+// Columns are in insertion order here (after pass_canon_kernel, before the gather into slot order). One workgroup per row; a 10 000-reference row is 10 kB of a matrix
+// of up to 1 GiB: 16-byte stores over the 16-byte aligned middle (rows start at any byte when n_refs is no multiple of 16), byte stores at the two ends.
+__global__ __launch_bounds__(256) void pass_triangle_kernel(uint8_t* __restrict__ pass, uint32_t n_refs, const long long* __restrict__ key, unsigned long long ref_base) {
+    const long long k = key[blockIdx.x];
+    if (k < 0 || (unsigned long long)k < ref_base) return;      // the row stays as it is / every reference is a later one
+    const unsigned long long d = (unsigned long long)k - ref_base;      // references [0, d] go
+    const uint32_t len = d >= n_refs ? n_refs : (uint32_t)d + 1u;
+    uint8_t* row = pass + (size_t)blockIdx.x * n_refs;
+    const uint32_t to16 = (16u - (uint32_t)((uintptr_t)row & 15u)) & 15u, head = to16 < len ? to16 : len;
+    const uint32_t n16 = (len - head) >> 4, tail = head + (n16 << 4);
+    if (threadIdx.x < head) row[threadIdx.x] = 0;
+    uint4* mid = (uint4*)(row + head);
+    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) mid[i] = make_uint4(0, 0, 0, 0);
+    if (threadIdx.x < len - tail) row[tail + threadIdx.x] = 0;
+}
 // ... and (row_blocks) the number of 2^BSI_BLOG-reference blocks that hold one of the query's passing references: what the slice join's plan looks at
 static_assert((1 << BSI_BLOG) == 256, "pass_count_kernel: one sweep of its 256 threads = one block of references");
 __global__ __launch_bounds__(256) void pass_count_kernel(const uint8_t* __restrict__ pass, uint32_t n_refs, uint32_t* __restrict__ row_count, uint8_t* __restrict__ col_flag, uint32_t* __restrict__ row_blocks) {

@@ -686,11 +686,12 @@ struct HitListT {
 using HitList = HitListT<psk_hit>;
 using HitListMin = HitListT<psk_hit_min>;      // the 20-byte records of psk_query_many_min: what the reference's Hit holds (hit.rs:77-104)
 // Database.query for n_queries sketches (lib.rs:569-659): hits of query i are all[offsets[i] .. offsets[i+1]), ref insertion order
+// keys (n_queries entries, or null) / ref_base: triangle mode - the pair (query i, reference r) is chained iff keys[i] < 0 or ref_base + r > keys[i] (pass_triangle_kernel)
 psk_status query_many_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o,
-                           HitList& all, uint64_t* offsets);
+                           HitList& all, uint64_t* offsets, const int64_t* keys = nullptr, uint64_t ref_base = 0);
 // ... the same with psk_hit_min records (query = index of the query within the call | learned << 31)
 psk_status query_many_min_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o,
-                               HitListMin& all, uint64_t* offsets);
+                               HitListMin& all, uint64_t* offsets, const int64_t* keys = nullptr, uint64_t ref_base = 0);
 psk_status chain_impl(Lane* ctx, const psk_sketch* const* refs, uint32_t n_refs,
                       const psk_sketch* query, const psk_query_opts* o, psk_hit* out);
 // Database.query from host bytes (lib.rs:549-660 with the _sketch call inside it): the one-launch-sequence path for a small genome

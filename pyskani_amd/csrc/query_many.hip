@@ -203,7 +203,7 @@ template <class H> struct RecPasses { __host__ __device__ bool operator()(const 
 
 template <class H>
 static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o,
-                               HitListT<H>& all, uint64_t* offsets) {
+                               HitListT<H>& all, uint64_t* offsets, const int64_t* keys, uint64_t ref_base) {
     hipStream_t st = ctx->stream;
     offsets[0] = 0;
     const Switches sw = Switches::read();      // ($PSK_*: once per call; the helper threads of the two-lane mode read this copy)
@@ -265,8 +265,9 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
     for (uint32_t b = 0; b < n_queries; b += QB) {
         const uint32_t m = std::min(QB, n_queries - b);
         // ---- screen: pass matrix on the device, counts + flags to the host
-        const size_t o_pass = 0, o_cnt = al256((size_t)m * n), o_flag = al256(o_cnt + 8 * (size_t)m), o_raw = al256(o_flag + n), o_end = o_raw + (loc ? (size_t)m * n : 0);      // (d_cnt: the queries' pass counts, then their counts of index blocks with a passing reference)
-        PSK_TRY(ctx->q_i.reserve(o_end + 256));
+        const size_t o_pass = 0, o_cnt = al256((size_t)m * n), o_flag = al256(o_cnt + 8 * (size_t)m), o_raw = al256(o_flag + n), o_end = o_raw + (loc ? (size_t)m * n : 0),      // (d_cnt: the queries' pass counts, then their counts of index blocks with a passing reference)
+                     o_key = al256(o_end), o_end_k = o_key + (keys ? 8 * (size_t)m : 0);      // (triangle mode: the round's keys)
+        PSK_TRY(ctx->q_i.reserve(o_end_k + 256));
         uint8_t* d_pass = (uint8_t*)ctx->q_i.p + o_pass; uint32_t* d_cnt = (uint32_t*)((char*)ctx->q_i.p + o_cnt); uint8_t* d_flag = (uint8_t*)ctx->q_i.p + o_flag;
         uint8_t* d_raw = loc ? (uint8_t*)ctx->q_i.p + o_raw : d_pass;      // (the screen's pass matrix, columns in insertion order)
         // a single query (psk_query: one contig against the database) is as slow as its chain of waits: its k-mer index is launched here,
@@ -278,6 +279,11 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
         ScreenStaging keep;
         PSK_TRY(screen_many_device(ctx, db, queries + b, m, screen_val, !o->faster_small, d_raw, keep, sw));
         if (db->has_dups) hipLaunchKernelGGL(pass_canon_kernel, dim3(m), dim3(256), 0, st, d_raw, n, (const uint32_t*)db->d_canon.p);
+        if (keys) {      // triangle mode: a row keeps the references behind its query's key (the caller's array outlives the copy: the call ends synchronised)
+            long long* d_key = (long long*)((char*)ctx->q_i.p + o_key);
+            PSK_HIP(hipMemcpyAsync(d_key, keys + b, 8 * (size_t)m, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(pass_triangle_kernel, dim3(m), dim3(256), 0, st, d_raw, n, (const long long*)d_key, (unsigned long long)ref_base);
+        }
         if (loc) pass_to_slots_launch(d_raw, d_pass, m, n, (const uint32_t*)db->d_ref_of.p, st);
         // ---- rescued short queries: exact anchor counts against every reference, pairs that cannot chain leave the pass matrix
         PoolScratch pf_buf;      // lives until the round's synchronisations are through, like the host arrays the copies read
@@ -908,9 +914,9 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
     }
     return PSK_OK;
 }
-psk_status query_many_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o, HitList& all, uint64_t* offsets) {
-    return query_many_t<psk_hit>(ctx, db, queries, n_queries, o, all, offsets);
+psk_status query_many_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o, HitList& all, uint64_t* offsets, const int64_t* keys, uint64_t ref_base) {
+    return query_many_t<psk_hit>(ctx, db, queries, n_queries, o, all, offsets, keys, ref_base);
 }
-psk_status query_many_min_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o, HitListMin& all, uint64_t* offsets) {
-    return query_many_t<psk_hit_min>(ctx, db, queries, n_queries, o, all, offsets);
+psk_status query_many_min_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o, HitListMin& all, uint64_t* offsets, const int64_t* keys, uint64_t ref_base) {
+    return query_many_t<psk_hit_min>(ctx, db, queries, n_queries, o, all, offsets, keys, ref_base);
 }

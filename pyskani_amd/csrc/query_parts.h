@@ -78,6 +78,7 @@ __global__ __launch_bounds__(256) void pair_build_rows_kernel(const BatchQ* __re
                                                               PairDesc* __restrict__ pairs, uint32_t* __restrict__ sbase, uint32_t* __restrict__ cbase,
                                                               uint2* __restrict__ pair_qr, uint32_t n_pairs, uint32_t n_items, uint32_t n_rows);
 __global__ __launch_bounds__(256) void pass_canon_kernel(uint8_t* __restrict__ pass, uint32_t n_refs, const uint32_t* __restrict__ canon);
+__global__ __launch_bounds__(256) void pass_triangle_kernel(uint8_t* __restrict__ pass, uint32_t n_refs, const long long* __restrict__ key, unsigned long long ref_base);
 __global__ __launch_bounds__(256) void pass_count_kernel(const uint8_t* __restrict__ pass, uint32_t n_refs, uint32_t* __restrict__ row_count, uint8_t* __restrict__ col_flag, uint32_t* __restrict__ row_blocks);
 constexpr size_t CHAIN_ANCHOR_WORDS = 14;      // u32 per anchor in Lane::q_d: the 16-byte record, the successor array, the serial DP's back-pointers, the 32-byte candidate record
 // device arrays of one chain launch sequence, carved from ctx->q_b

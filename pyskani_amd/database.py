@@ -684,15 +684,28 @@ class Database:
         n = len(self._names)
         return (C.c_void_p * max(n, 1))(*[self._lib.psk_db_sketch(self._h, i) for i in range(n)])
 
-    def query_handles(self, handles, n, *, learned_ani=None, median=False, robust=False, cutoff=None, faster_small=False, raw=False):
+    def query_handles(self, handles, n, *, learned_ani=None, median=False, robust=False, cutoff=None, faster_small=False, raw=False, keys=None, ref_base=0):
         """psk_query_many_min over n raw sketch handles -> (records, offsets): a numpy array of 20-byte psk_hit_min records (own memory;
         `query` = index of the hit's query among the handles, bit 31 = learned) and the n+1 int64 offsets of every query's hits in it.
-        raw=True: psk_query_many, the 80-byte psk_hit records with every chaining integer (parity tests)."""
+        raw=True: psk_query_many, the 80-byte psk_hit records with every chaining integer (parity tests).
+        keys (n integers) / ref_base: triangle mode (psk_query_many_tri, psk_query_many_tri_min) - the pair (query i, reference r) is chained iff keys[i] < 0 or
+        ref_base + r > keys[i]; what remains are the records of the call without keys, in the same order."""
         opts = self._opts(learned_ani, median, robust, cutoff, faster_small)
+        c_keys = None
+        if keys is not None:
+            c_keys = np.ascontiguousarray(keys, dtype=np.int64)
+            if c_keys.ndim != 1 or len(c_keys) != n:
+                raise ValueError(f"keys must hold one integer per query: {n} expected, {c_keys.size} given")
+            if int(ref_base) < 0:
+                raise ValueError("ref_base must not be negative")
         with Database._Borrow(self, False):
             hits_p = C.POINTER(_capi.Hit if raw else _capi.HitMin)()
             offs = (C.c_uint64 * (n + 1))()
-            _capi.check((self._lib.psk_query_many if raw else self._lib.psk_query_many_min)(self._h, handles, n, C.byref(opts), C.byref(hits_p), offs))
+            if c_keys is None:
+                _capi.check((self._lib.psk_query_many if raw else self._lib.psk_query_many_min)(self._h, handles, n, C.byref(opts), C.byref(hits_p), offs))
+            else:
+                _capi.check((self._lib.psk_query_many_tri if raw else self._lib.psk_query_many_tri_min)(
+                    self._h, handles, n, c_keys.ctypes.data_as(C.POINTER(C.c_int64)), int(ref_base), C.byref(opts), C.byref(hits_p), offs))
             try:
                 total = int(offs[n])
                 recs = _capi.hit_records(hits_p, 0, total, self._HIT_DTYPE if raw else self._HIT_MIN_DTYPE)
@@ -700,6 +713,30 @@ class Database:
                 if hits_p:
                     self._lib.psk_free(hits_p)
         return recs, np.frombuffer(offs, dtype=np.uint64).astype(np.int64)
+
+    def triangle_records(self, *, learned_ani=None, median=False, robust=False, cutoff=None, faster_small=False, raw=False):
+        """The database's own all-vs-all with every unordered pair chained ONCE and no genome against itself (skani's `triangle`): genome i - insertion index - is the
+        query of every pair (i, j) with j > i. Returns (records, offsets) as `query_handles` does: psk_hit_min records (psk_hit with raw=True) in ascending
+        (query, ref_index) order, `query` (`reserved` in raw records) = the query's insertion index, and len(self) + 1 offsets. A record is the record the full
+        all-vs-all `query_handles(self.sketch_handles(), len(self))` holds for that (query, reference): the pairs left out are masked on the device before the
+        chain stage, nothing is swapped or recomputed. `triangle_matrix` turns the records into the dense symmetric form."""
+        if self._n_lazy:
+            raise RuntimeError("triangle_records needs a memory-resident database")
+        n = len(self._names)
+        if len(set(self._names)) != n:      # (a name's hits go to its LAST sketch: "the later reference" of a pair is not defined then)
+            raise ValueError("triangle_records: a name was sketched more than once; which sketch of it is the later reference is ambiguous")
+        if n < 2:
+            return np.zeros(0, self._HIT_DTYPE if raw else self._HIT_MIN_DTYPE), np.zeros(n + 1, np.int64)
+        recs, offs = self.query_handles(self.sketch_handles(), n, learned_ani=learned_ani, median=median, robust=robust, cutoff=cutoff, faster_small=faster_small,
+                                        raw=raw, keys=np.arange(n, dtype=np.int64), ref_base=0)
+        if raw:      # (the library clears `reserved`; psk_hit_min's `query` is the index within the call already)
+            recs["reserved"] = np.repeat(np.arange(n, dtype=np.uint32), np.diff(offs))
+        return recs, offs
+
+    def triangle(self, *, learned_ani=None, median=False, robust=False, cutoff=None, faster_small=False):
+        """`triangle_records` as a list of `Hit` lists indexed by insertion index: entry i holds genome i's hits against the genomes added after it."""
+        recs, offs = self.triangle_records(learned_ani=learned_ani, median=median, robust=robust, cutoff=cutoff, faster_small=faster_small, raw=True)
+        return [self._hits(recs[offs[i]:offs[i + 1]], self._names[i]) if offs[i + 1] > offs[i] else [] for i in range(len(self._names))]
 
     def query_records(self, name, *contigs, seed=True, learned_ani=None, median=False, robust=False, cutoff=None, faster_small=False):
         """Database.query returning the psk_hit records (numpy structured array, ref_index = insertion index) instead of `Hit`s."""
@@ -798,3 +835,22 @@ class Database:
             return r
         recs = self._query_host(contigs, seed, opts)
         return self._hits(recs, name) if len(recs) else []
+
+
+def triangle_matrix(records, n):
+    """Dense form of triangle records (`Database.triangle_records`, `ShardedDatabase.all_vs_all_records(triangle=True)`; either record dtype) over n genomes:
+    `(ani, af)`, both float32 of shape (n, n). For a hit (i, j): ani[i, j] = ani[j, i] = its ANI, af[i, j] = af_query and af[j, i] = af_ref - af[x, y] is the
+    fraction of x aligned to y. The diagonal is 1.0, a pair without a hit 0.0; `np.tril(ani)` is the layout skani's `triangle` prints. Host-side numpy only."""
+    names = records.dtype.names
+    q = (records["query"] & np.uint32(0x7FFFFFFF)).astype(np.int64) if "query" in names else records["reserved"].astype(np.int64)
+    r = records["ref_index"].astype(np.int64)
+    n = int(n)
+    if len(records) and (int(q.max()) >= n or int(r.max()) >= n):
+        raise ValueError(f"a record's index is beyond n = {n}")
+    ani = np.zeros((n, n), np.float32)
+    af = np.zeros((n, n), np.float32)
+    ani[q, r] = records["ani"]; ani[r, q] = records["ani"]
+    af[q, r] = records["af_query"]; af[r, q] = records["af_ref"]
+    d = np.arange(n)
+    ani[d, d] = 1.0; af[d, d] = 1.0
+    return ani, af

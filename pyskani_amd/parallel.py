@@ -385,7 +385,7 @@ class ShardedDatabase:
         base = Hit.__mro__[1]      # (the storage class takes `learned`; Hit's own constructor is the reference's five arguments, hit.rs:26-33)
         return [base.__new__(Hit, float(r["ani"]), name, float(r["af_query"]), self.names[int(r["ref_index"])], float(r["af_ref"]), bool(l)) for r, l in zip(got, learned.tolist())]
 
-    def all_vs_all_records(self, batch=1024, overlap=True, **opts):
+    def all_vs_all_records(self, batch=1024, overlap=True, triangle=False, **opts):
         """Every genome of the job against every other (and itself), as RECORDS: a numpy array of psk_hit_min (psk_hit with `raw`)
         sorted by (query, reference) with GLOBAL indices (`query` - `reserved` in raw records - and `ref_index`), identical on every rank.
 
@@ -396,7 +396,13 @@ class ShardedDatabase:
         issued (on a helper thread: its collectives and the library's packing run on their own streams) BEFORE round b is queried,
         so the exchange leaves the critical path: two rounds' gathered sketches are alive at a time. `batch` = 1 024: a round of ~5 Mb genomes (1 024 x its ~100 relatives x 40 000
         seeds) is then above the 2^31 (pair, seed) items from which the library keeps two batches in flight on two lanes; at 256 a rank ran every round as one chain (single-GPU
-        emulation of a rank's share of the 10 000-genome job, bench.py extras.scaling_model: 70 against 77 ms per rank at N = 8). 2 x 1 024 x N packed sketches of 0.9 MB are alive: 14 GB at N = 8."""
+        emulation of a rank's share of the 10 000-genome job, bench.py extras.scaling_model: 70 against 77 ms per rank at N = 8). 2 x 1 024 x N packed sketches of 0.9 MB are alive: 14 GB at N = 8.
+
+        `triangle`: every unordered pair once and no genome against itself - the records (q, r) with r > q of the call without it, unchanged (the library's triangle mode:
+        a round's queries carry their global indices as keys, the shard its first global index as the reference base). The triangle's pairs are NOT balanced over the
+        ranks: a rank chains its shard against the queries with lower global indices only, so the rank that holds the highest indices chains the most and the one that
+        holds the lowest little more than its own shard's triangle. What that imbalance costs has not been measured, and evening it out is not part of this mode (any
+        rule that changes which genome of a pair is the query changes the hits)."""
         t_all = time.perf_counter()
         local = self.local
         n_local = len(local)
@@ -439,8 +445,11 @@ class ShardedDatabase:
                 if total and failure is None:
                     if trace is not None:
                         trace.append(("query_start", b))
+                    # global query index of every query: the batch's queries are rank-major, rank r contributes counts[r]
+                    qglob = np.concatenate([self._shard(r)[0] + b * batch + np.arange(counts[r], dtype=np.int64) for r in range(self.world)])
+                    tri = {"keys": qglob, "ref_base": self._lo} if triangle else {}
                     try:
-                        recs, offs = self._timed("psk_s", local.query_handles, handles, total, raw=self.raw, **opts)
+                        recs, offs = self._timed("psk_s", local.query_handles, handles, total, raw=self.raw, **tri, **opts)
                     except Exception as e:      # a rank whose local query failed keeps entering the remaining collectives (its peers are waiting in them) with nothing to add, and raises at the end
                         failure = e
                         lib.psk_sketch_free_many(handles, total)
@@ -448,8 +457,6 @@ class ShardedDatabase:
                         continue
                     if trace is not None:
                         trace.append(("query_end", b))
-                    # global query index of every hit: the batch's queries are rank-major, rank r contributes counts[r]
-                    qglob = np.concatenate([self._shard(r)[0] + b * batch + np.arange(counts[r], dtype=np.int64) for r in range(self.world)])
                     if qf == "query":      # the library numbered the hits' queries within the call; bit 31 (learned) rides along
                         q = recs["query"]
                         recs["query"] = (qglob[q & QUERY_MASK].astype(np.uint32) | (q & np.uint32(0x80000000)))
@@ -480,9 +487,10 @@ class ShardedDatabase:
         self.stats["total_s"] += time.perf_counter() - t_all
         return out
 
-    def all_vs_all(self, batch=1024, **opts):
-        """`all_vs_all_records` as {query_name: [Hit, ...]}, identical on every rank, hits in global reference order."""
-        recs = self.all_vs_all_records(batch=batch, **opts)
+    def all_vs_all(self, batch=1024, triangle=False, **opts):
+        """`all_vs_all_records` as {query_name: [Hit, ...]}, identical on every rank, hits in global reference order. `triangle`: a genome's hits against the genomes
+        after it in the global order only (see `all_vs_all_records` for what that does to the ranks' balance)."""
+        recs = self.all_vs_all_records(batch=batch, triangle=triangle, **opts)
         from .database import Hit
         out = {n: [] for n in self.names}
         names = self.names

@@ -125,6 +125,12 @@ extern "C" {
                           hits: *mut *mut PskHit, offsets: *mut u64) -> c_int;
     pub fn psk_query_many_min(db: *mut PskDb, qs: *const *const PskSketch, n: u32, o: *const PskQueryOpts,
                               hits: *mut *mut PskHitMin, offsets: *mut u64) -> c_int;
+    // triangle mode: (query i, reference r) is chained iff key[i] < 0 or ref_base + r > key[i] (key[i] = i, ref_base = 0: every unordered pair of the database once).
+    // Added after PSK_ABI_VERSION 7 without raising it: look the two symbols up before relying on them when the library may be older
+    pub fn psk_query_many_tri(db: *mut PskDb, qs: *const *const PskSketch, n: u32, key: *const i64, ref_base: u64, o: *const PskQueryOpts,
+                              hits: *mut *mut PskHit, offsets: *mut u64) -> c_int;
+    pub fn psk_query_many_tri_min(db: *mut PskDb, qs: *const *const PskSketch, n: u32, key: *const i64, ref_base: u64, o: *const PskQueryOpts,
+                                  hits: *mut *mut PskHitMin, offsets: *mut u64) -> c_int;
     // the locality order of the references (slot_of: psk_db_size entries or null)
     pub fn psk_db_locality(db: *mut PskDb, slot_of: *mut u32, n_groups: *mut u32, is_identity: *mut u32) -> c_int;
     // the two halves of `query`, for a disk-backed Database (markers resident, sketches loaded per query)
