@@ -103,7 +103,7 @@ const char* psk_version(void);
 /* The C-ABI's revision: raised whenever an entry point's parameters or a structure's layout change (4: psk_sketch_unpack takes the extent of its source buffer as third
  * argument; 5: psk_hit_min / psk_query_many_min / psk_gather_hits_min / psk_ctx_join_work added;
  * 6: psk_db_locality added; 7: psk_ctx_rerun_stats added). psk_query_many_tri and psk_query_many_tri_min came after 7 WITHOUT raising it: no existing argument
- * list or structure moved, and a binding that wants them detects them by their presence (dlsym). A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
+ * list or structure moved, and a binding that wants them detects them by their presence (dlsym); psk_cluster_records and psk_ctx_cluster_stats likewise. A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
  * written against before it calls anything else: an argument list that moved is a memory error, not a link error. */
 #define PSK_ABI_VERSION 7
 int psk_abi_version(void);
@@ -321,6 +321,33 @@ psk_status psk_query_many_tri(psk_db* db, const psk_sketch* const* queries, uint
                               const psk_query_opts* opts, psk_hit** hits, uint64_t* offsets);
 psk_status psk_query_many_tri_min(psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const int64_t* query_key, uint64_t ref_base,
                                   const psk_query_opts* opts, psk_hit_min** hits, uint64_t* offsets);
+
+/* ---- the cluster stage: representatives and clusters from the records of an all-vs-all (csrc/cluster.hip). Dereplication as it is done with skani's `triangle` output:
+ * one representative per group of genomes above an ANI / aligned-fraction threshold, every other genome assigned to a representative.
+ * Input: n_recs records over n_genomes genomes - a triangle or a full all-vs-all; a pair may appear in either direction, in both, or repeatedly. q = query & 0x7FFFFFFF
+ * (bit 31 is the `learned` flag), r = ref_index; an index of n_genomes or more is PSK_EINVAL. A record QUALIFIES iff q != r, ani >= (float)min_ani and the aligned-fraction
+ * rule holds - af_rule 0: af_query >= (float)min_af and af_ref >= (float)min_af, 1: one of the two - every comparison in float; a NaN fails its comparison. The unordered
+ * pair {q, r} is an EDGE iff one of its records qualifies, and its weight is the largest ani among those.
+ * Order: genome a precedes b iff priority[a] > priority[b], or the priorities are equal and a < b; priority == NULL: insertion order, genome 0 first.
+ * linkage 0 (greedy): walk the genomes in that order; one with an edge to a representative is a member, any other becomes a representative (the lexicographically-first
+ *   maximal independent set). Then every member goes to its adjacent representative of largest weight - any adjacent one, also one that comes after the member in the
+ *   order; ties to the earlier representative. rep_of[rep] = rep, rep_ani[rep] = 1; a member's rep_ani is the weight of the edge to its representative.
+ * linkage 1 (single): the connected components; rep_of[v] = the component's first genome in the order, rep_ani[v] = 1 for it, else the weight of the direct edge to it, 0
+ *   without one.
+ * The result is a function of the input alone. recs, priority and the outputs are host memory (rep_of, rep_ani: n_genomes entries); *n_reps = genomes with rep_of[v] == v.
+ * n_recs >= 2^30 or n_genomes >= 2^31: PSK_ELIMIT. n_recs == 0: every genome represents itself, without a device call. */
+typedef struct {
+    double  min_ani;   /* <= 0: 0.95 */
+    double  min_af;    /* < 0: 0.5; 0: no aligned-fraction condition */
+    int32_t af_rule;   /* 0: both fractions, 1: either */
+    int32_t linkage;   /* 0: greedy representatives, 1: single linkage */
+} psk_cluster_opts;
+psk_status psk_cluster_records(psk_ctx* ctx, const psk_hit_min* recs, uint64_t n_recs, uint32_t n_genomes,
+                               const uint64_t* priority /* n_genomes values or NULL */, const psk_cluster_opts* opts,
+                               uint32_t* rep_of, float* rep_ani /* may be NULL */, uint32_t* n_reps /* may be NULL */);
+/* Measurement: the context's last psk_cluster_records call that reached the device - undirected edges of its graph, greedy rounds that decided a vertex (linkage 0),
+ * hook passes that joined two labels (linkage 1). Any pointer may be NULL. */
+psk_status psk_ctx_cluster_stats(psk_ctx* ctx, uint64_t* edges, uint64_t* rounds, uint64_t* hook_passes);
 
 #ifdef __cplusplus
 }

@@ -111,6 +111,8 @@ struct psk_ctx {
     // batches of the chain stage sent round again, by cause: anchor capacity / wide join format / the index join's count pass / a pipeline batch handed back to the
     // one-chain loop (psk_ctx_rerun_stats; counted where the host decides, read by tests - no decision reads them)
     std::atomic<uint64_t> rr_cap{0}, rr_wide{0}, rr_onepass{0}, rr_refit{0};
+    // the cluster stage's last call (cluster.hip; psk_ctx_cluster_stats): undirected edges, greedy rounds that decided a vertex, hook passes of single linkage
+    std::atomic<uint64_t> cl_edges{0}, cl_rounds{0}, cl_hooks{0};
     // lanes: created on demand, at most max_lanes; a call takes a free one (LaneGuard) and gives it back
     std::mutex lanes_mu;
     std::condition_variable lanes_cv;

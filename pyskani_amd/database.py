@@ -733,6 +733,31 @@ class Database:
             recs["reserved"] = np.repeat(np.arange(n, dtype=np.uint32), np.diff(offs))
         return recs, offs
 
+    def dereplicate(self, *, min_ani=0.95, min_af=0.5, af="both", linkage="greedy", priority="length", learned_ani=None, median=False, robust=False, cutoff=None,
+                    faster_small=False):
+        """One representative per group of genomes above an ANI / aligned-fraction threshold, every other genome assigned to a representative: `triangle_records`,
+        then `cluster_records` (whose docstring gives the rule). priority="length": each reference's total kept-contig length (psk_sketch_info), so the longest
+        genome of a group represents it; None: insertion order; an array of len(self) unsigned integers: used as given (larger is better, ties to the earlier
+        genome). Returns a `Dereplication`. The restrictions of `triangle_records` hold: a memory-resident database, no name sketched twice.
+        A sharded run holds the same gathered records on every rank (`ShardedDatabase.all_vs_all_records(triangle=True)`): pass them to `cluster_records`."""
+        _cluster_args(af, linkage)
+        n = len(self._names)
+        if isinstance(priority, str):
+            if priority != "length":
+                raise ValueError(f"priority must be 'length', None or an array of {n} integers, not {priority!r}")
+        elif priority is not None:
+            priority = _cluster_priority(priority, n)
+        recs, _ = self.triangle_records(learned_ani=learned_ani, median=median, robust=robust, cutoff=cutoff, faster_small=faster_small)
+        if isinstance(priority, str):
+            with Database._Borrow(self, False):
+                tl = C.c_uint64()
+                priority = np.empty(n, np.uint64)
+                for i in range(n):
+                    _capi.check(self._lib.psk_sketch_info(self._lib.psk_db_sketch(self._h, i), None, None, None, C.byref(tl), None))
+                    priority[i] = tl.value
+        rep_of, rep_ani = cluster_records(recs, n, min_ani=min_ani, min_af=min_af, af=af, linkage=linkage, priority=priority, device=self._device)
+        return Dereplication(rep_of, rep_ani, list(self._names), priority)
+
     def triangle(self, *, learned_ani=None, median=False, robust=False, cutoff=None, faster_small=False):
         """`triangle_records` as a list of `Hit` lists indexed by insertion index: entry i holds genome i's hits against the genomes added after it."""
         recs, offs = self.triangle_records(learned_ani=learned_ani, median=median, robust=robust, cutoff=cutoff, faster_small=faster_small, raw=True)
@@ -854,3 +879,78 @@ def triangle_matrix(records, n):
     d = np.arange(n)
     ani[d, d] = 1.0; af[d, d] = 1.0
     return ani, af
+
+
+_CLUSTER_AF = {"both": 0, "either": 1}
+_CLUSTER_LINKAGE = {"greedy": 0, "single": 1}
+
+
+def _cluster_args(af, linkage):
+    if af not in _CLUSTER_AF:
+        raise ValueError(f"af must be 'both' or 'either', not {af!r}")
+    if linkage not in _CLUSTER_LINKAGE:
+        raise ValueError(f"linkage must be 'greedy' or 'single', not {linkage!r}")
+    return _CLUSTER_AF[af], _CLUSTER_LINKAGE[linkage]
+
+
+def _cluster_priority(priority, n):
+    prio = np.asarray(priority)
+    if prio.ndim != 1 or len(prio) != n:
+        raise ValueError(f"priority must hold one integer per genome: {n} expected, {prio.size} given")
+    if prio.dtype.kind not in "ui" or (prio.dtype.kind == "i" and len(prio) and int(prio.min()) < 0):
+        raise ValueError("priority must hold unsigned integers")
+    return np.ascontiguousarray(prio, dtype=np.uint64)
+
+
+def cluster_records(records, n, *, min_ani=0.95, min_af=0.5, af="both", linkage="greedy", priority=None, device=0):
+    """Representatives and clusters of n genomes from the psk_hit_min records of their all-vs-all (`Database.triangle_records`, a full `query_handles` run, or the
+    gathered records of a sharded run, which are the same on every rank) -> `(rep_of, rep_ani)`, uint32 and float32 arrays of n entries. Runs on the GPU
+    (psk_cluster_records).
+
+    With q = query & 0x7FFFFFFF and r = ref_index, a record qualifies iff q != r, ani >= float32(min_ani) and both (af="both") or one (af="either") of af_query and
+    af_ref >= float32(min_af); min_af=0: no aligned-fraction condition; a NaN fails its comparison. The pair {q, r} is an edge iff one of its records - in either
+    direction, repeated or not - qualifies; its weight is the largest such ani. An index of n or more raises ValueError.
+    Genome a precedes b iff priority[a] > priority[b], or they are equal and a < b (priority=None: insertion order).
+    linkage="greedy": in that order, a genome with an edge to a representative is a member, any other becomes a representative; every member is then assigned to its
+    adjacent representative of largest weight (any adjacent one; ties to the earlier in the order). rep_of[rep] = rep and rep_ani[rep] = 1; a member's rep_ani is the
+    weight of the edge to its representative.
+    linkage="single": connected components, represented by their first genome in the order; rep_ani = 1 for it, else the weight of the direct edge to it, 0 without one."""
+    af_rule, link = _cluster_args(af, linkage)
+    if not isinstance(records, np.ndarray) or records.dtype != Database._HIT_MIN_DTYPE:
+        raise ValueError("records must be a numpy array of psk_hit_min records (the dtype of Database.triangle_records)")
+    if records.ndim != 1:
+        raise ValueError("records must be one-dimensional")
+    n = int(n)
+    if n < 0 or n >= 1 << 31:
+        raise ValueError(f"n = {n}")
+    prio = None if priority is None else _cluster_priority(priority, n)
+    recs = np.ascontiguousarray(records)
+    lib = _capi.load()
+    ctx = default_context(device)
+    rep_of, rep_ani = np.empty(n, np.uint32), np.empty(n, np.float32)
+    opts = _capi.ClusterOpts(float(min_ani), float(min_af), af_rule, link)
+    _capi.check(lib.psk_cluster_records(ctx._h, recs.ctypes.data if len(recs) else None, len(recs), n, None if prio is None else prio.ctypes.data, C.byref(opts),
+                                        rep_of.ctypes.data, rep_ani.ctypes.data, None))
+    return rep_of, rep_ani
+
+
+class Dereplication:
+    """What `Database.dereplicate` returns: `rep_of[i]` = index of genome i's representative (its own for a representative), `rep_ani[i]` = the ANI that assigned it
+    (1.0 for a representative), `representatives` = their ascending indices, `names` = their names, `priority` = the priorities used (None: insertion order)."""
+
+    def __init__(self, rep_of, rep_ani, all_names, priority=None):
+        self.rep_of, self.rep_ani, self.priority = rep_of, rep_ani, priority
+        self.representatives = np.flatnonzero(rep_of == np.arange(len(rep_of), dtype=np.uint32)).astype(np.uint32)
+        self.names = [all_names[int(i)] for i in self.representatives]
+
+    def clusters(self):
+        """{representative index: ascending array of its members' indices, itself included}"""
+        order = np.argsort(self.rep_of, kind="stable")
+        reps, first = np.unique(self.rep_of[order], return_index=True)
+        return {int(r): m.astype(np.uint32) for r, m in zip(reps, np.split(order, first[1:]))}
+
+    def __len__(self):
+        return len(self.representatives)
+
+    def __repr__(self):
+        return f"Dereplication({len(self.rep_of)} genomes, {len(self.representatives)} representatives)"

@@ -34,6 +34,9 @@ pub struct PskHit {
 /// psk_hit_min: what `Hit` holds (hit.rs:77-104) in 20 bytes; `query` = index of the query within the call, bit 31 = the model produced `ani`
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct PskHitMin { pub ani: f32, pub af_query: f32, pub af_ref: f32, pub ref_index: u32, pub query: u32 }
+/// psk_cluster_opts: min_ani <= 0 means 0.95; min_af < 0 means 0.5, 0 no aligned-fraction condition; af_rule 0 both / 1 either; linkage 0 greedy / 1 single
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct PskClusterOpts { pub min_ani: f64, pub min_af: f64, pub af_rule: i32, pub linkage: i32 }
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct PskSeed { pub kmer: u32, pub pos: u32, pub contig: u32, pub canon: u32 }
 #[repr(C)] #[derive(Clone, Copy)]
@@ -131,6 +134,11 @@ extern "C" {
                               hits: *mut *mut PskHit, offsets: *mut u64) -> c_int;
     pub fn psk_query_many_tri_min(db: *mut PskDb, qs: *const *const PskSketch, n: u32, key: *const i64, ref_base: u64, o: *const PskQueryOpts,
                                   hits: *mut *mut PskHitMin, offsets: *mut u64) -> c_int;
+    // the cluster stage: representatives (greedy) or connected components (single linkage) from the records of an all-vs-all; host arrays in and out. Added after
+    // PSK_ABI_VERSION 7 without raising it, like the two above
+    pub fn psk_cluster_records(ctx: *mut PskCtx, recs: *const PskHitMin, n_recs: u64, n_genomes: u32, priority: *const u64, opts: *const PskClusterOpts,
+                               rep_of: *mut u32, rep_ani: *mut f32, n_reps: *mut u32) -> c_int;
+    pub fn psk_ctx_cluster_stats(ctx: *mut PskCtx, edges: *mut u64, rounds: *mut u64, hook_passes: *mut u64) -> c_int;
     // the locality order of the references (slot_of: psk_db_size entries or null)
     pub fn psk_db_locality(db: *mut PskDb, slot_of: *mut u32, n_groups: *mut u32, is_identity: *mut u32) -> c_int;
     // the two halves of `query`, for a disk-backed Database (markers resident, sketches loaded per query)
