@@ -420,7 +420,8 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
                 const int xt_force = sw.lane_xtrees.force();
                 const bool xtrees = xt_force >= 0 ? xt_force == 1 : n_items / n_pairs > (1u << 20);
                 const auto lane_k = A.band <= 20 && xtrees ? (gsl ? chain_lane20x_kernel<true> : chain_lane20x_kernel<false>)
-                                  : A.band <= 20 ? (gsl ? chain_lane20_kernel<true> : chain_lane20_kernel<false>) : (gsl ? chain_lane_kernel<true> : chain_lane_kernel<false>);
+                                  : A.band == 20 && gsl ? chain_lane20_kernel<true, true>      // (the band fills the window: no distance test per pair; the 16-byte records' instance would spill six registers for it and keeps the test)
+                                  : A.band <= 20 ? (gsl ? chain_lane20_kernel<true, false> : chain_lane20_kernel<false, false>) : (gsl ? chain_lane_kernel<true> : chain_lane_kernel<false>);
                 hipLaunchKernelGGL(lane_k, dim3((waves + LANE_WAVES - 1) / LANE_WAVES), dim3(64 * LANE_WAVES), 0, st, A, rpw);
             }
             // the few chunks it passes on (more than LANE_TREES trees, >= 16 384 anchors): wave kernel over the list

@@ -71,4 +71,19 @@ __device__ __forceinline__ int32_t lane_eval2(uint32_t qx, uint32_t ux, uint32_t
     const uint32_t key = ((uint32_t)s1 << 7) + ((((uint32_t)ANCHOR_SCORE2 + 1u) << 7) | (127u - (uint32_t)d));      // scores stay below 2^20 (a chunk holds < 16 384 anchors): the key's sign bit is free
     return (int32_t)(key | (bad & 0x80000000u));
 }
-
+// The same for the slice join's 8-byte anchors: wx = q | m << 16, the anchor's own low word (m = ref contig << 1 | strand), and y.q1 = (q + 1) | m << 16.
+// Equal m: wx - y.q1 is dq - 1 as before. Different m: the high halves differ by at least 2^16 and the low ones by at most FRAGMENT_LENGTH + 1, so the
+// difference is below -(BP_CHAIN_BAND) or above BP_CHAIN_BAND - 1 and one of the two range tests on a fails: no test on m of its own, and y.m is not read.
+static_assert(FRAGMENT_LENGTH + 1u < (1u << 16) && (1u << 16) - (FRAGMENT_LENGTH + 1u) > (uint32_t)BP_CHAIN_BAND, "q + 1 stays in the low half; another contig or strand is out of the q range");
+__device__ __forceinline__ int32_t lane_eval2_qm(uint32_t wx, uint32_t ux, const LanePred& y, int d) {
+    const int32_t a = (int32_t)(wx - y.q1);                               // dq - 1, or out of range
+    const int32_t t = (int32_t)(ux - y.u), nt = (int32_t)(y.u - ux);
+    const int32_t gap = t > nt ? t : nt;
+    const int32_t b = a - t;
+    const int32_t s1 = y.f1 - gap;
+    const uint32_t bad = (uint32_t)a | (uint32_t)(BP_CHAIN_BAND - 1 - a) | (uint32_t)b | (uint32_t)(MAX_GAP_LENGTH - gap) | (uint32_t)s1;
+    const uint32_t key = ((uint32_t)s1 << 7) + ((((uint32_t)ANCHOR_SCORE2 + 1u) << 7) | (127u - (uint32_t)d));
+    return (int32_t)(key | (bad & 0x80000000u));
+}
+// q + 1 of a window entry (QM: the low half of its first register)
+template <bool QM> __device__ __forceinline__ uint32_t lane_q1(const LanePred& y) { return QM ? y.q1 & 0xFFFFu : y.q1; }

@@ -266,7 +266,7 @@ __global__ __launch_bounds__(64) void chunk_hops_items_kernel(const uint32_t* __
                                                                const PairDesc* __restrict__ pairs, const uint32_t* __restrict__ sbase, const uint32_t* __restrict__ cbase,
                                                                uint32_t n_pairs, uint32_t* __restrict__ slice_cnt, uint2* __restrict__ scratch, uint32_t* __restrict__ err);
 // the DP kernels: PK = the slice join's 8-byte anchors (ChainArgs::anc), else the 16-byte records
-template <bool PK> __global__ __launch_bounds__(64 * LANE_WAVES) __attribute__((amdgpu_waves_per_eu(3, 8))) void chain_lane20_kernel(ChainArgs A, uint32_t rows_per_wave);
+template <bool PK, bool BW> __global__ __launch_bounds__(64 * LANE_WAVES) __attribute__((amdgpu_waves_per_eu(3, 8))) void chain_lane20_kernel(ChainArgs A, uint32_t rows_per_wave);
 template <bool PK> __global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane20x_kernel(ChainArgs A, uint32_t rows_per_wave);
 template <bool PK> __global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane_kernel(ChainArgs A, uint32_t rows_per_wave);
 template <bool PK> __global__ __launch_bounds__(64 * LANE_WAVES) void chain_quad_kernel(ChainArgs A);

@@ -63,7 +63,7 @@ __device__ uint32_t chain_chunk_serial(const ChainArgs& A, uint32_t s, uint32_t 
 #define LANE_PK_LD 4
 #endif
 static_assert(LANE_PK_LD == 2 || LANE_PK_LD == 4, "eight or sixteen 8-byte anchors per load");
-template <int W, int XT, bool PK>      // window depth: the band rounded up to a multiple of four (20 at c = 125; 24 covers c >= 105); PK: the slice join's 8-byte anchors
+template <int W, int XT, bool PK, bool BW>      // BW: the band equals W (every window entry is within it); window depth: the band rounded up to a multiple of four (20 at c = 125; 24 covers c >= 105); PK: the slice join's 8-byte anchors
 __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32_t rows_per_wave) {
     __shared__ uint32_t s_rd[LANE_WAVES][32][64];     // tree id << 14 | depth of the last 32 anchors, per lane
     __shared__ unsigned long long s_xk[LANE_WAVES][XT ? XT : 1][XT ? 64 : 1];     // slots 4 .. 4 + XT - 1: best anchor key
@@ -90,9 +90,12 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
     const AncRd<PK> anc{A.anc};
     const uint32_t s_al = s & ~(4u * LD - 1u);
     const uint32_t len = mine ? e - s_al : 0;          // steps this lane takes part in (the first s - s_al are idle)
+    const uint32_t off = s - s_al, n_own = mine ? e - s : 0;      // step t holds the chunk's anchor t - off, if that is below n_own
+    // 8-byte anchors (PK): a window entry keeps (q + 1) | (ref contig | strand) << 16 in ONE register - the anchor word's own layout - and the pair's
+    // q difference and contig / strand test are one subtraction (lane_eval2_qm): 60 window registers instead of 80, three instructions fewer per pair
     LanePred P[W];
 #pragma unroll
-    for (int i = 0; i < W; i++) { P[i].q1 = 0; P[i].u = 0; P[i].m = 0xFFFFFFFFu; P[i].f1 = -1; }      // (score - 1 of an EMPTY entry: below every real one, see the far bound)
+    for (int i = 0; i < W; i++) { P[i].q1 = 0; P[i].u = 0; P[i].m = 0xFFFFFFFFu; P[i].f1 = -1; }      // (score - 1 of an EMPTY entry: below every real one, see the far bound; PK: m is not kept)
     // Chain trees that can yield a candidate, at most LANE_TREES per chunk, keyed by the local index of their ROOT
     // anchor. A tree gets a slot when its first anchor with score >= MIN_SCORE2 appears (such an anchor has depth >= 3,
     // and lower-scoring anchors can never be the tree's best once one exists); the many single-anchor trees of
@@ -103,6 +106,11 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
     for (int j = 0; j < LANE_TREES; j++) { bk[j] = 0; sroot[j] = 0xFFFFFFFFu; }
     uint32_t S = 0;
     bool ovf = false;
+    // Slot cache: along a chain one qualifying anchor after the other belongs to the same tree, so slot 0 is kept as the tree of the PREVIOUS qualifying
+    // anchor and an anchor of that tree costs one compare and one 64-bit maximum. An anchor of another tree takes the find-or-allocate path under its own
+    // exec mask and leaves its tree in slot 0 (a tree found in slot j changes places with slot 0; a new tree sends slot 0's to the free slot S). Which
+    // slot a tree sits in is of no account: a slot is still taken at the first qualifying anchor of a tree, S and ovf count as before, and the candidates
+    // leave in ROOT order whatever the slots' order (below). (Not for XT: its slots in LDS stay as they are.)
     uint32_t (*rd)[64] = s_rd[wave];      // root index << 14 | depth of the last 32 anchors
     const int band = A.band;
     // The FAR part of the band - predecessors more than LANE_NEAR anchors back - is scored only where it could win (the rule of chain_quad_deep_kernel): a
@@ -113,6 +121,18 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
     constexpr bool prune = XT == 0;
     constexpr int NR = LANE_NEAR;
     uint32_t far_diag = 0;
+    // The exact bound ftop[u] - the largest f - 1 among the far entries of anchor u that lie within BP_CHAIN_BAND of the step's first anchor - is a pass over
+    // the window, and along a chain nobody asks for it. mfar, a running maximum of f - 1 over every entry that has turned far, filters or not, stands in:
+    // ftop[u] <= mfar, so an anchor whose near score reaches mfar + 1 + ANCHOR_SCORE2 passes the exact test as well. Only when some lane fails that, with its
+    // far_diag bit set and its nearest far entry in reach, is ftop worked out - once per step of four anchors, for the whole wave, kept up entry by entry
+    // for the step's remaining anchors - and the decision taken from it: the lanes that ask are a superset of those the exact rule lets through, so the
+    // wave scores the far part exactly when it did before.
+    // A step that worked ftop out leaves mfar = its ftop[3], not the running maximum: a chain that broke leaves scores in mfar that nothing reaches any
+    // more, and every anchor of the new chain would ask again until the chunk ends. ftop[3] still bounds every later anchor's far set: that set holds
+    // entries of this step's P[NR - 3 .. W - 1] and anchors yet to come. The latter enter mfar as they turn far. Of the former, ftop[3] leaves out what has
+    // no score (f - 1 = -1, never above any bound) and what lies more than BP_CHAIN_BAND before this step's first anchor - anchors of a chunk come in query
+    // order (the serial rule's break relies on it), so those lie as far before every later step's first anchor and its ftop leaves them out as well.
+    int32_t mfar = -1;
     for (uint32_t tb = 0; __any(tb < len); tb += 4 * LD) {
       uint4 aw[LD][AncRd<PK>::W4];      // the raw words; an anchor is decoded once, in its step
 #pragma unroll
@@ -125,10 +145,17 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
       for (int h = 0; h < LD; h++) {
         uint4 an4[4];      // (q, r, ref contig | strand, -)
         AncRd<PK>::unpack4(aw[h], an4);
-        const uint32_t t0 = tb + 4u * h, x0 = s_al + t0;
+        const uint32_t t0 = tb + 4u * h;
         const uint32_t qs[4] = {an4[0].x, an4[1].x, an4[2].x, an4[3].x}, rs[4] = {an4[0].y, an4[1].y, an4[2].y, an4[3].y}, ms[4] = {an4[0].z, an4[1].z, an4[2].z, an4[3].z};
         LanePred nw[4];
-        int32_t ftop[4] = {-1, -1, -1, -1};      // largest f - 1 among the far entries of the step's anchor u: P[NR - u .. W - 1]
+        // mu: the bound on the far entries' f - 1 for the step's anchor u, whose far entries are P[NR - u .. W - 1]. exact (wave-uniform): mu is the largest
+        // among those within BP_CHAIN_BAND of the step's FIRST anchor; else it is the running maximum, filter or not
+        // (only entries within BP_CHAIN_BAND of the step's first anchor count - the later ones lie further on: where anchors are sparse, pairs 10 % apart,
+        // a chain that broke at a long gap leaves its high scores in the window for twenty anchors, out of reach but above everything the new chain has)
+        const uint32_t q0 = qs[0] + 1u;
+        auto in_reach = [&](const LanePred& y) -> int32_t { return q0 - lane_q1<PK>(y) <= (uint32_t)BP_CHAIN_BAND ? y.f1 : -1; };
+        bool exact = false;
+        int32_t mu = mfar;      // the running maximum up to the step's anchor u
         if (prune) {
             if ((t0 & 63u) == 0) {
                 far_diag = 0;
@@ -138,72 +165,106 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
 #pragma unroll
                 for (int i = NR - 3; i <= NR; i++) far_diag |= __builtin_amdgcn_alignbit(3u, 3u, 32u - (((P[i].u - (uint32_t)MAX_GAP_LENGTH) >> 10) & 31u));      // the four that turned far
             }
-            // (only entries within BP_CHAIN_BAND of the step's FIRST anchor count - the later ones lie further on: where anchors are sparse, pairs 10 % apart,
-            // a chain that broke at a long gap leaves its high scores in the window for twenty anchors, out of reach but above everything the new chain has)
-            const uint32_t q0 = qs[0] + 1u;
-            int32_t m = -1;
-#pragma unroll
-            for (int i = NR; i < W; i++) { const int32_t f = q0 - P[i].q1 <= (uint32_t)BP_CHAIN_BAND ? P[i].f1 : -1; m = f > m ? f : m; }
-            ftop[0] = m;
-#pragma unroll
-            for (int u = 1; u < 4; u++) { const int32_t f = q0 - P[NR - u].q1 <= (uint32_t)BP_CHAIN_BAND ? P[NR - u].f1 : -1; m = f > m ? f : m; ftop[u] = m; }
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            const uint32_t x = x0 + u, t = t0 + u;
-            const bool act = x >= s && x < e && mine;
+            const uint32_t t = t0 + u, xl = t - off;      // xl: the anchor's index within the chunk
+            const bool act = xl < n_own;
             const uint32_t qx = qs[u], rx = rs[u], mx = ms[u];
             const uint32_t ux = lane_diag(qx, rx, 0u - (mx & 1u));
+            const uint32_t wx = PK ? qx | (mx << 16) : qx;      // (PK: the anchor's own low word)
             int32_t best = 0;
 #pragma unroll
             for (int d = 1; d <= NR; d++) {
-                if (d <= band) {
-                    const int32_t k = d <= u ? lane_eval2(qx, ux, mx, nw[u - d], d) : lane_eval2(qx, ux, mx, P[d - 1 - u], d);
+                if (BW || d <= band) {
+                    const LanePred& y = d <= u ? nw[u - d] : P[d - 1 - u];
+                    const int32_t k = PK ? lane_eval2_qm(wx, ux, y, d) : lane_eval2(qx, ux, mx, y, d);
                     best = k > best ? k : best;
                 }
             }
             // (... and the far entries lie further back on the query than the nearest of them: none is within BP_CHAIN_BAND if that one is not - sparse anchors,
             // pairs 10 % apart, restart their chains every few anchors and would otherwise ask for the far part each time)
-            if (!prune || __any(act && ftop[u] >= 0 && (best >> 7) < ftop[u] + 1 + ANCHOR_SCORE2 && ((far_diag >> ((ux >> 10) & 31u)) & 1u) && qx + 1u - P[NR - u].q1 <= (uint32_t)BP_CHAIN_BAND)) {
+            bool far = !prune;
+            if (prune) {
+                const bool geo = act && ((far_diag >> ((ux >> 10) & 31u)) & 1u) && qx + 1u - lane_q1<PK>(P[NR - u]) <= (uint32_t)BP_CHAIN_BAND;
+                if (exact) { const int32_t f = in_reach(P[NR - u]); mu = f > mu ? f : mu; }
+                else {
+                    mu = P[NR - u].f1 > mu ? P[NR - u].f1 : mu;
+                    if (__any(geo && (best >> 7) < mu + 1 + ANCHOR_SCORE2)) {      // some lane may need its far part: the bound itself, once per step
+                        mu = -1;
+#pragma unroll
+                        for (int i = NR - u; i < W; i++) { const int32_t f = in_reach(P[i]); mu = f > mu ? f : mu; }
+                        exact = true;
+                    }
+                }
+                far = exact && __any(geo && mu >= 0 && (best >> 7) < mu + 1 + ANCHOR_SCORE2);
+            }
+            if (far) {
 #pragma unroll
                 for (int d = NR + 1; d <= W; d++) {
-                    if (d <= band) {
-                        const int32_t k = lane_eval2(qx, ux, mx, P[d - 1 - u], d);
+                    if (BW || d <= band) {
+                        const int32_t k = PK ? lane_eval2_qm(wx, ux, P[d - 1 - u], d) : lane_eval2(qx, ux, mx, P[d - 1 - u], d);
                         best = k > best ? k : best;
                     }
                 }
             }
-            int32_t f = ANCHOR_SCORE2; uint32_t ridx = x - s, dep = 1;
+            int32_t f = ANCHOR_SCORE2; uint32_t ridx = xl, dep = 1;
             if (best > 0) {
                 f = best >> 7;
                 const uint32_t v = rd[(t - (127u - ((uint32_t)best & 127u))) & 31u][lane];
                 ridx = v >> 14; dep = (v & 16383u) + 1;
             }
             rd[t & 31u][lane] = (ridx << 14) | dep;
-            nw[u].q1 = qx + 1u; nw[u].u = ux; nw[u].m = act ? mx : 0xFFFFFFFFu; nw[u].f1 = act ? f - 1 : -1;
+            nw[u].q1 = wx + 1u; nw[u].u = ux; nw[u].m = act ? mx : 0xFFFFFFFFu; nw[u].f1 = act ? f - 1 : -1;      // (PK: an entry that is not the chunk's has no score, which bars it)
             if (act && f >= MIN_SCORE2) {
-                const unsigned long long k64 = ((unsigned long long)(uint32_t)f << 28) | ((unsigned long long)(16383u - (x - s)) << 14) | dep;
-                bool found = false;
+                const unsigned long long k64 = ((unsigned long long)(uint32_t)f << 28) | ((unsigned long long)(16383u - xl) << 14) | dep;
+                if (XT == 0) {
+                    if (sroot[0] == ridx) bk[0] = k64 > bk[0] ? k64 : bk[0];
+                    else {
+                        bool found = false;
 #pragma unroll
-                for (int j = 0; j < LANE_TREES; j++) {
-                    const bool hit = sroot[j] == ridx;
-                    found = found || hit;
-                    if (hit && k64 > bk[j]) bk[j] = k64;
-                }
-                if (XT && !found && S > (uint32_t)LANE_TREES) {      // the LDS slots (a lane's own column: no other lane touches it)
-                    const uint32_t nx = S - LANE_TREES < (uint32_t)XT ? S - LANE_TREES : (uint32_t)XT;
-                    for (uint32_t j = 0; j < nx; j++)
-                        if (s_xr[wave][j][lane] == ridx) { found = true; if (k64 > s_xk[wave][j][lane]) s_xk[wave][j][lane] = k64; break; }
-                }
-                if (!found) {
-                    if (S >= (uint32_t)(LANE_TREES + XT)) ovf = true;
-                    else if (XT && S >= (uint32_t)LANE_TREES) { s_xr[wave][S - LANE_TREES][lane] = ridx; s_xk[wave][S - LANE_TREES][lane] = k64; }
+                        for (int j = 1; j < LANE_TREES; j++) {
+                            const bool hit = sroot[j] == ridx;      // (roots are distinct, and ridx is none of the empty slots' 0xFFFFFFFF)
+                            found = found || hit;
+                            const uint32_t r0 = sroot[0]; const unsigned long long b0 = bk[0];
+                            sroot[0] = hit ? sroot[j] : r0; bk[0] = hit ? bk[j] : b0;
+                            sroot[j] = hit ? r0 : sroot[j]; bk[j] = hit ? b0 : bk[j];
+                        }
+                        if (found) bk[0] = k64 > bk[0] ? k64 : bk[0];
+                        else {
+                            if (S >= (uint32_t)LANE_TREES) ovf = true;
+                            else {
 #pragma unroll
-                    for (int j = 0; j < LANE_TREES; j++) if (S == (uint32_t)j) { sroot[j] = ridx; bk[j] = k64; }
-                    S++;
+                                for (int j = 1; j < LANE_TREES; j++) if (S == (uint32_t)j) { sroot[j] = sroot[0]; bk[j] = bk[0]; }
+                                sroot[0] = ridx; bk[0] = k64;
+                            }
+                            S++;
+                        }
+                    }
+                } else {      // the Gb-scale kernel: four slots in registers and XT in LDS, searched in order
+                    bool found = false;
+#pragma unroll
+                    for (int j = 0; j < LANE_TREES; j++) {
+                        const bool hit = sroot[j] == ridx;
+                        found = found || hit;
+                        if (hit && k64 > bk[j]) bk[j] = k64;
+                    }
+                    if (XT && !found && S > (uint32_t)LANE_TREES) {      // the LDS slots (a lane's own column: no other lane touches it)
+                        const uint32_t nx = S - LANE_TREES < (uint32_t)XT ? S - LANE_TREES : (uint32_t)XT;
+                        for (uint32_t j = 0; j < nx; j++)
+                            if (s_xr[wave][j][lane] == ridx) { found = true; if (k64 > s_xk[wave][j][lane]) s_xk[wave][j][lane] = k64; break; }
+                    }
+                    if (!found) {
+                        if (S >= (uint32_t)(LANE_TREES + XT)) ovf = true;
+                        else if (XT && S >= (uint32_t)LANE_TREES) { s_xr[wave][S - LANE_TREES][lane] = ridx; s_xk[wave][S - LANE_TREES][lane] = k64; }
+#pragma unroll
+                        for (int j = 0; j < LANE_TREES; j++) if (S == (uint32_t)j) { sroot[j] = ridx; bk[j] = k64; }
+                        S++;
+                    }
                 }
             }
         }
+        mfar = mu;
         // shift the register window by four anchors
 #pragma unroll
         for (int i = W - 1; i >= 4; i--) P[i] = P[i - 4];
@@ -212,7 +273,7 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
     }
     if ((uint32_t)lane < rows_per_wave && slot < A.n_rows && real) {
         if (mine && !ovf) {
-            // candidates in ROOT order (slots were taken in order of first qualifying anchor): pick the smallest root left
+            // candidates in ROOT order, whichever slot a tree sits in: pick the smallest root left
             uint32_t nc = 0, last = 0;
             const uint32_t q0 = PK ? A.row_q0[slot].x : 0u;      // (8-byte anchors: q positions leave absolute)
             for (uint32_t c = 0; c < S; c++) {
@@ -246,12 +307,13 @@ __device__ __forceinline__ void chain_lane_body(const ChainArgs& A, const uint32
 
 // W = 20 fits three waves per SIMD (168 registers; the 24-deep window needs 192 and runs two): the kernel is VALU-issue bound and
 // a third wave fills issue slots that two leave empty
+// BW: the launch's band is the window's 20 (c = 125: the default) - narrower bands (c > 125) take the instance that tests each pair's distance
+template <bool PK, bool BW>
+__global__ __launch_bounds__(64 * LANE_WAVES) __attribute__((amdgpu_waves_per_eu(3, 8))) void chain_lane20_kernel(ChainArgs A, uint32_t rows_per_wave) { chain_lane_body<20, 0, PK, BW>(A, rows_per_wave); }
 template <bool PK>
-__global__ __launch_bounds__(64 * LANE_WAVES) __attribute__((amdgpu_waves_per_eu(3, 8))) void chain_lane20_kernel(ChainArgs A, uint32_t rows_per_wave) { chain_lane_body<20, 0, PK>(A, rows_per_wave); }
+__global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane20x_kernel(ChainArgs A, uint32_t rows_per_wave) { chain_lane_body<20, LANE_XTREES, PK, false>(A, rows_per_wave); }
 template <bool PK>
-__global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane20x_kernel(ChainArgs A, uint32_t rows_per_wave) { chain_lane_body<20, LANE_XTREES, PK>(A, rows_per_wave); }
-template <bool PK>
-__global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane_kernel(ChainArgs A, uint32_t rows_per_wave) { chain_lane_body<LANE_N, 0, PK>(A, rows_per_wave); }
+__global__ __launch_bounds__(64 * LANE_WAVES) void chain_lane_kernel(ChainArgs A, uint32_t rows_per_wave) { chain_lane_body<LANE_N, 0, PK, false>(A, rows_per_wave); }
 
 // ---- four lanes per chunk, for launches too small to fill the chip with one lane per chunk -----------------
 // (the headline search: 100 pairs = 22 k chunks). Lane j of a quad owns the anchors whose index is j mod 4: ownership
@@ -879,11 +941,12 @@ __global__ __launch_bounds__(64 * CHAIN_WAVES) void chain_wave_reg_kernel(ChainA
 
 // (launched from chain.hip: the 16-byte records of the per-pair and contig joins, and the slice join's 8-byte anchors)
 #define PSK_DP_FORMS(PK) \
-    template __global__ void chain_lane20_kernel<PK>(ChainArgs, uint32_t); template __global__ void chain_lane20x_kernel<PK>(ChainArgs, uint32_t); \
+    template __global__ void chain_lane20_kernel<PK, false>(ChainArgs, uint32_t); template __global__ void chain_lane20x_kernel<PK>(ChainArgs, uint32_t); \
     template __global__ void chain_lane_kernel<PK>(ChainArgs, uint32_t); template __global__ void chain_quad_kernel<PK>(ChainArgs); \
     template __global__ void chain_quad_deep_kernel<PK>(ChainArgs); template __global__ void chain_chunk_kernel<PK>(ChainArgs); \
     template __global__ void chain_chunk_list_kernel<PK>(ChainArgs); \
     template __global__ void chain_wave_reg_kernel<1, PK>(ChainArgs); template __global__ void chain_wave_reg_kernel<2, PK>(ChainArgs);
 PSK_DP_FORMS(false)
 PSK_DP_FORMS(true)
+template __global__ void chain_lane20_kernel<true, true>(ChainArgs, uint32_t);      // band == window: 8-byte anchors only (chain.hip)
 #undef PSK_DP_FORMS
