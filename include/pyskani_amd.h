@@ -103,7 +103,7 @@ const char* psk_version(void);
 /* The C-ABI's revision: raised whenever an entry point's parameters or a structure's layout change (4: psk_sketch_unpack takes the extent of its source buffer as third
  * argument; 5: psk_hit_min / psk_query_many_min / psk_gather_hits_min / psk_ctx_join_work added;
  * 6: psk_db_locality added; 7: psk_ctx_rerun_stats added). psk_query_many_tri and psk_query_many_tri_min came after 7 WITHOUT raising it: no existing argument
- * list or structure moved, and a binding that wants them detects them by their presence (dlsym); psk_cluster_records and psk_ctx_cluster_stats likewise. A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
+ * list or structure moved, and a binding that wants them detects them by their presence (dlsym); psk_cluster_records, psk_ctx_cluster_stats and psk_ctx_tier_stats likewise. A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
  * written against before it calls anything else: an argument list that moved is a memory error, not a link error. */
 #define PSK_ABI_VERSION 7
 int psk_abi_version(void);
@@ -137,6 +137,13 @@ psk_status psk_ctx_small_query_stats(psk_ctx* ctx, uint64_t* taken, uint64_t* re
  * in the one-walk index join and the batch took the count pass; `refit`: a batch of the two-lane pipeline was handed back to the one-chain loop (a wide request,
  * too many anchors for one launch, or no memory). Read-only: no decision depends on them. Any pointer may be NULL. */
 psk_status psk_ctx_rerun_stats(psk_ctx* ctx, uint64_t* cap, uint64_t* wide, uint64_t* onepass, uint64_t* refit, int reset);
+/* Measurement: which size tiers of the chain selection and of the per-pair reduce the chain stage launched since the last reset, and how many pairs its selection
+ * lists held. out[0..n) receives, in this order (entries beyond the eleventh are zero): launches of select_tiny_kernel, pair_empty_kernel, pair_reduce_tiny_kernel,
+ * pair_reduce_small_kernel, pair_reduce_wave_kernel, pair_reduce_kernel and pair_reduce_large_kernel (a batch that is sent round again launches again); then, summed
+ * over the completed batches, the pairs in the live list, the pairs the lane-per-pair selection left to the wave kernels, the pairs passed to the second selection tier
+ * (more than 512 candidate chains) and to the workgroup tier (more than 1024). Read-only: no decision depends on them. Added after ABI 7 without raising it: a binding
+ * detects it by its presence. */
+psk_status psk_ctx_tier_stats(psk_ctx* ctx, uint64_t* out, int n, int reset);
 /* Host-side 2-bit packing of the ingest pipeline (csrc/pack_host.cpp), exposed for tests: n ASCII bases -> ceil(n / 16) words, the first base in a
  * word's highest two bits; A 0, C 1, G 2, T 3, case-insensitive, every other byte 0 (the codes of the sketch kernels). mode 0: the best
  * implementation the CPU has (AVX-512BW), 1: the scalar one. */

@@ -59,7 +59,7 @@ class Seed(C.Structure):
 # every symbol include/pyskani_amd.h declares
 SYMBOLS = [
     "psk_last_error", "psk_version", "psk_abi_version", "psk_free", "psk_ctx_create", "psk_ctx_destroy",
-    "psk_ctx_synchronize", "psk_pack2bit_host", "psk_ctx_small_query_stats", "psk_ctx_rerun_stats", "psk_ctx_set_timing", "psk_ctx_timing", "psk_db_add_batch", "psk_device_alloc", "psk_device_free", "psk_memcpy_h2d",
+    "psk_ctx_synchronize", "psk_pack2bit_host", "psk_ctx_small_query_stats", "psk_ctx_rerun_stats", "psk_ctx_tier_stats", "psk_ctx_set_timing", "psk_ctx_timing", "psk_db_add_batch", "psk_device_alloc", "psk_device_free", "psk_memcpy_h2d",
     "psk_sketch_host", "psk_sketch_many_host", "psk_sketch_batch_device", "psk_sketch_free", "psk_sketch_free_many", "psk_sketch_info",
     "psk_sketch_export", "psk_sketch_contig_lens", "psk_sketch_import", "psk_db_create", "psk_db_destroy", "psk_db_add", "psk_db_size",
     "psk_db_name", "psk_db_sketch", "psk_db_locality", "psk_screen", "psk_chain", "psk_query", "psk_query_host", "psk_query_many", "psk_query_many_min", "psk_query_many_tri", "psk_query_many_tri_min", "psk_cluster_records", "psk_ctx_cluster_stats", "psk_gather_hits_min",
@@ -94,6 +94,8 @@ def load():
     lib.psk_ctx_synchronize.argtypes = [vp]
     lib.psk_ctx_small_query_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     lib.psk_ctx_rerun_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.c_int]
+    if hasattr(lib, "psk_ctx_tier_stats"):      # (came after ABI 7 without raising it: detected by its presence)
+        lib.psk_ctx_tier_stats.argtypes = [vp, C.POINTER(u64), C.c_int, C.c_int]
     lib.psk_pack2bit_host.argtypes = [vp, u64, vp, C.c_int]
     lib.psk_pack2bit_host.restype = None
     lib.psk_ctx_set_timing.argtypes = [vp, C.c_int]

@@ -248,6 +248,12 @@ psk_status psk_ctx_rerun_stats(psk_ctx* c, uint64_t* cap, uint64_t* wide, uint64
     if (reset) { c->rr_cap = 0; c->rr_wide = 0; c->rr_onepass = 0; c->rr_refit = 0; }
     return PSK_OK;
 }
+psk_status psk_ctx_tier_stats(psk_ctx* c, uint64_t* out, int n, int reset) {
+    if (!c || (n > 0 && !out)) { psk_set_error("NULL argument"); return PSK_EINVAL; }
+    for (int i = 0; i < n; i++) out[i] = i < TIER_COUNT ? c->tier[i].load() : 0;
+    if (reset) for (int i = 0; i < TIER_COUNT; i++) c->tier[i] = 0;
+    return PSK_OK;
+}
 psk_status psk_device_alloc(psk_ctx* c, size_t bytes, void** dptr) {
     if (!c || !dptr) { psk_set_error("device_alloc: NULL argument"); return PSK_EINVAL; }
     PSK_HIP(hipSetDevice(c->device));

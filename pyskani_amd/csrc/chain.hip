@@ -470,7 +470,7 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
     {   // batches of pairs with short chunk tables (contigs): one lane per pair first; PSK_SELECT_TINY=0 leaves every pair to the wave kernels
         SA.tiny_done = use_live && !force_serial && !sw.select_tiny.off() && n_rows / n_pairs < 16;
         SA.rest_list = (uint32_t*)L.hits_sel; SA.rest_count = L.misc + 13;      // (hits_sel: free until the hits are selected; misc was zeroed by pair_table_kernel)
-        if (SA.tiny_done) hipLaunchKernelGGL(select_tiny_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, SA);
+        if (SA.tiny_done) { ctx->dev->tier[TIER_SELECT_TINY]++; hipLaunchKernelGGL(select_tiny_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, SA); }
     }
     // (the list of the second tier lives in huge_list: select_big_kernel only writes that after select_mid_kernel has read it)
     hipLaunchKernelGGL(select_kernel, dim3(std::min<uint32_t>(n_pairs, 16384u)), dim3(64), 0, st, SA, L.huge_list, L.misc + 14);
@@ -537,7 +537,7 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
     }
     ctx->t_begin(K_PAIR_REDUCE);
     R.live = use_live ? L.live : nullptr; R.n_live = L.misc + 9;
-    if (use_live) hipLaunchKernelGGL(pair_empty_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, R, n_pairs);
+    if (use_live) { ctx->dev->tier[TIER_PAIR_EMPTY]++; hipLaunchKernelGGL(pair_empty_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, R, n_pairs); }
     // many pairs with short chunk tables (contigs): one wave per pair first; the workgroup-per-pair kernel then only sees the long tables
     const bool no_small = sw.reduce_small.off();
     // tables of 65 .. 512 rows (pairs of ~5 Mb genomes: ~250): one wave per pair, eight rows per lane; PSK_REDUCE_WAVE=0 leaves them to the workgroup kernel (tests, A/B)
@@ -548,14 +548,14 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
     // contig batches with the mean ANI: pairs of up to four chunk rows by one lane each first (PSK_REDUCE_TINY=0: by a wave each)
     const bool no_tiny = sw.reduce_tiny.off();
     R.tiny_done = R.small_done && !no_tiny && !o->median && !o->robust && n_rows / n_pairs < 16;
-    if (R.tiny_done) hipLaunchKernelGGL(pair_reduce_tiny_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, R, n_pairs);
-    if (R.small_done) hipLaunchKernelGGL(pair_reduce_small_kernel, dim3(std::min<uint32_t>((n_pairs + 3) / 4, 8192u)), dim3(256), 0, st, R, n_pairs);
-    if (R.wave_done) hipLaunchKernelGGL(pair_reduce_wave_kernel, dim3(std::min<uint32_t>((n_pairs + 3) / 4, 16384u)), dim3(256), 0, st, R, n_pairs);
+    if (R.tiny_done) { ctx->dev->tier[TIER_REDUCE_TINY]++; hipLaunchKernelGGL(pair_reduce_tiny_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, R, n_pairs); }
+    if (R.small_done) { ctx->dev->tier[TIER_REDUCE_SMALL]++; hipLaunchKernelGGL(pair_reduce_small_kernel, dim3(std::min<uint32_t>((n_pairs + 3) / 4, 8192u)), dim3(256), 0, st, R, n_pairs); }
+    if (R.wave_done) { ctx->dev->tier[TIER_REDUCE_WAVE]++; hipLaunchKernelGGL(pair_reduce_wave_kernel, dim3(std::min<uint32_t>((n_pairs + 3) / 4, 16384u)), dim3(256), 0, st, R, n_pairs); }
     // (when no pair of the batch can have more rows than the wave kernels take - contigs have 1-3 chunks, 5 Mb genomes ~250 - the two
     // workgroup-per-pair kernels would only walk the pairs to find that out: 24 ms per 17 M contig pairs)
     if (!((R.small_done && L.rows_pair_max <= 64u) || (R.small_done && R.wave_done && L.rows_pair_max <= 64u * RW_PER)))
-        hipLaunchKernelGGL(pair_reduce_kernel, dim3(std::min<uint32_t>(n_pairs, 8192u)), dim3(256), 0, st, R, n_pairs);
-    if (n_rows > (size_t)RED_SMALL && L.rows_pair_max > (uint32_t)RED_SMALL) hipLaunchKernelGGL(pair_reduce_large_kernel, dim3(std::min<uint32_t>(n_pairs, 512u)), dim3(256), 0, st, R, n_pairs);      // some pair may have more than RED_SMALL rows: a small grid walks the list for them
+        { ctx->dev->tier[TIER_REDUCE_GROUP]++; hipLaunchKernelGGL(pair_reduce_kernel, dim3(std::min<uint32_t>(n_pairs, 8192u)), dim3(256), 0, st, R, n_pairs); }
+    if (n_rows > (size_t)RED_SMALL && L.rows_pair_max > (uint32_t)RED_SMALL) { ctx->dev->tier[TIER_REDUCE_LARGE]++; hipLaunchKernelGGL(pair_reduce_large_kernel, dim3(std::min<uint32_t>(n_pairs, 512u)), dim3(256), 0, st, R, n_pairs); }      // some pair may have more than RED_SMALL rows: a small grid walks the list for them
     ctx->t_end();
     // measurement (timers on): candidate chains and live chunk-table rows of the batch, for the selection's and the reduce's byte counts
     if (ctx->dev->timing) hipLaunchKernelGGL(work_rows_kernel, dim3((uint32_t)std::min<size_t>((n_rows + 255) / 256, 2048)), dim3(256), 0, st, (const ChunkOut*)L.cout, (const uint32_t*)L.nch, (const uint32_t*)L.cbase, (const uint32_t*)L.row_pair, (uint32_t)n_rows, (unsigned long long*)(L.misc + 20));
@@ -644,7 +644,7 @@ psk_status chain_batch(Lane* ctx, const HostPair* hp, uint32_t n_pairs, const ps
         bool retry; const bool was_wide = wide;
         PSK_TRY(chain_check(*T, n_pairs, &cap, &wide, &retry));
         count_rerun(ctx->dev, was_wide, wide, retry);
-        if (!retry) { ctx->dev->w_pairs += n_pairs; ctx->dev->w_items += items; ctx->dev->w_anchors += T->total64; ctx->dev->w_cands += T->cands; ctx->dev->w_rows += T->rows; break; }
+        if (!retry) { ctx->dev->w_pairs += n_pairs; ctx->dev->w_items += items; ctx->dev->w_anchors += T->total64; ctx->dev->w_cands += T->cands; ctx->dev->w_rows += T->rows; count_tier_pairs(ctx->dev, T->misc); break; }
         if (attempt >= 3) { psk_set_error("internal: anchor capacity did not converge"); return PSK_EHIP; }
     }
     for (uint32_t p = 0; p < n_pairs; p++) { out[p] = h_hits[p]; out[p].reserved = 0; }

@@ -95,6 +95,8 @@ struct TimerRec { int id; hipEvent_t a, b; };
 // stream, scratch buffers and pinned staging, so that calls from different host threads overlap on the device (the reference's
 // `query` takes &self and releases the GIL, lib.rs:551,569: concurrent queries are its only route to parallelism).
 struct Lane;
+// psk_ctx_tier_stats: the order of its counters
+enum { TIER_SELECT_TINY = 0, TIER_PAIR_EMPTY, TIER_REDUCE_TINY, TIER_REDUCE_SMALL, TIER_REDUCE_WAVE, TIER_REDUCE_GROUP, TIER_REDUCE_LARGE, TIER_PAIRS_LIVE, TIER_PAIRS_REST, TIER_PAIRS_MID, TIER_PAIRS_BIG, TIER_COUNT };
 struct psk_ctx {
     int device = 0;
     bool timing = false;
@@ -111,6 +113,9 @@ struct psk_ctx {
     // batches of the chain stage sent round again, by cause: anchor capacity / wide join format / the index join's count pass / a pipeline batch handed back to the
     // one-chain loop (psk_ctx_rerun_stats; counted where the host decides, read by tests - no decision reads them)
     std::atomic<uint64_t> rr_cap{0}, rr_wide{0}, rr_onepass{0}, rr_refit{0};
+    // launches of the selection's and the reduce's size tiers, and the pairs a completed batch's status words name for the selection's lists (psk_ctx_tier_stats;
+    // counted where the host decides or reads the status it copies back anyway, read by tests - no decision reads them)
+    std::atomic<uint64_t> tier[TIER_COUNT] = {};
     // the cluster stage's last call (cluster.hip; psk_ctx_cluster_stats): undirected edges, greedy rounds that decided a vertex, hook passes of single linkage
     std::atomic<uint64_t> cl_edges{0}, cl_rounds{0}, cl_hooks{0};
     // lanes: created on demand, at most max_lanes; a call takes a free one (LaneGuard) and gives it back

@@ -612,7 +612,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                     std::vector<BatchQ> bqs; std::vector<uint2> tab, ebase; std::vector<uint32_t> qn;      // (host copies feed asynchronous copies: alive until the job is reaped)
                     uint64_t pairs = 0, items = 0, rows = 0, rows_pair_max = 0;
                     psk_status rc = PSK_OK; bool refit = false; char err[512] = "";
-                    std::vector<H> hits; uint64_t anchors = 0, cands = 0, wrows = 0, visited = 0, lookups = 0;
+                    std::vector<H> hits; uint64_t anchors = 0, cands = 0, wrows = 0, visited = 0, lookups = 0; uint32_t misc[16] = {};
                 };
                 PipeJob job[2];
                 std::thread th[2];
@@ -694,7 +694,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                             PSK_HIP(hipStreamSynchronize(s2));
                             J.hits.assign(h_sel, h_sel + n_sel);
                         }
-                        J.anchors = T->total64; J.cands = T->cands; J.wrows = T->rows; J.visited = T->visited;
+                        J.anchors = T->total64; J.cands = T->cands; J.wrows = T->rows; J.visited = T->visited; memcpy(J.misc, T->misc, sizeof J.misc);
                         J.lookups = 0; for (const BatchQ& e : J.bqs) J.lookups += h_qd[e.q].n;
                         return PSK_OK;
                     }();
@@ -719,7 +719,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                         for (size_t i = 0; i < nh; i++) { H& h = all.p[all.n + i]; if (loc) h.ref_index = db->ref_of[h.ref_index]; const uint32_t lq = HitRec<H>::local_query(h); q_hits[lq]++; HitRec<H>::finish(h, b + lq); }
                         all.n += nh;
                     }
-                    ctx->dev->w_pairs += J.pairs; ctx->dev->w_items += J.items; ctx->dev->w_anchors += J.anchors; ctx->dev->w_cands += J.cands; ctx->dev->w_rows += J.wrows;
+                    ctx->dev->w_pairs += J.pairs; ctx->dev->w_items += J.items; ctx->dev->w_anchors += J.anchors; ctx->dev->w_cands += J.cands; ctx->dev->w_rows += J.wrows; count_tier_pairs(ctx->dev, J.misc);
                     ctx->dev->w_lookups += J.lookups; ctx->dev->w_visited += J.visited;
                     return PSK_OK;
                 };
@@ -880,7 +880,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                     PSK_TRY(rc);
                     if (!retry && L.gsi_onepass && (T->misc[0] & 4u)) { L.gsi_onepass = false; retry = true; ctx->dev->rr_onepass++; }      // a pair with more anchors than query seeds: with the count pass
                     if (!retry) {
-                        ctx->dev->w_pairs += n_pairs; ctx->dev->w_items += items; ctx->dev->w_anchors += T->total64; ctx->dev->w_cands += T->cands; ctx->dev->w_rows += T->rows;
+                        ctx->dev->w_pairs += n_pairs; ctx->dev->w_items += items; ctx->dev->w_anchors += T->total64; ctx->dev->w_cands += T->cands; ctx->dev->w_rows += T->rows; count_tier_pairs(ctx->dev, T->misc);
                         if (round_gsi) { uint64_t lk = 0; for (const BatchQ& e : bqs) lk += h_qd[e.q].n; ctx->dev->w_lookups += lk; ctx->dev->w_visited += T->visited; }
                         break;
                     }

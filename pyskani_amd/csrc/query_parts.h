@@ -108,6 +108,9 @@ struct ChainTail { uint32_t misc[16]; unsigned long long total64, visited, cands
 psk_status chain_check(const ChainTail& T, uint32_t n_pairs, uint64_t* cap, bool* wide, bool* retry);
 // psk_ctx_rerun_stats: what chain_check asked for after an attempt in the format `was_wide` (counted, never read back)
 static inline void count_rerun(psk_ctx* dev, bool was_wide, bool wide, bool retry) { if (wide && !was_wide) dev->rr_wide++; else if (retry) dev->rr_cap++; }
+// psk_ctx_tier_stats: launches by kernel (chain_run), then the pairs of every completed batch the live list held (misc[9]), the lane selection left to the wave tiers
+// (misc[13]), the first wave tier passed to the second (misc[14]) and the second to the workgroup tier (misc[10])
+static inline void count_tier_pairs(psk_ctx* dev, const uint32_t* misc) { dev->tier[TIER_PAIRS_LIVE] += misc[9]; dev->tier[TIER_PAIRS_REST] += misc[13]; dev->tier[TIER_PAIRS_MID] += misc[14]; dev->tier[TIER_PAIRS_BIG] += misc[10]; }
 struct HostPair { const psk_sketch* r; const psk_sketch* q; };
 psk_status chain_batch(Lane* ctx, const HostPair* hp, uint32_t n_pairs, const psk_query_opts* o, psk_hit* out, const Switches& sw);
 

@@ -108,6 +108,7 @@ extern "C" {
     // database: markers.push + sketches.store (lib.rs:501-508)
     pub fn psk_ctx_small_query_stats(ctx: *mut PskCtx, taken: *mut u64, rerun: *mut u64, general: *mut u64) -> c_int;
     pub fn psk_ctx_rerun_stats(ctx: *mut PskCtx, cap: *mut u64, wide: *mut u64, onepass: *mut u64, refit: *mut u64, reset: c_int) -> c_int;
+    pub fn psk_ctx_tier_stats(ctx: *mut PskCtx, out: *mut u64, n: c_int, reset: c_int) -> c_int;
     pub fn psk_pack2bit_host(src: *const u8, n: u64, dst: *mut u32, mode: c_int);
     pub fn psk_db_create(ctx: *mut PskCtx, p: *const PskParams, out: *mut *mut PskDb) -> c_int;
     pub fn psk_db_destroy(db: *mut PskDb);
