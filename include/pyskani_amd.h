@@ -286,6 +286,15 @@ const psk_sketch* psk_db_sketch(const psk_db* db, uint32_t index);
  * slot_of[i] = position of reference i (psk_db_size entries, or NULL), *n_groups = groups of relatives found, *is_identity = 1 when the order is the insertion
  * order (the references' groups were contiguous already, the database fits one index block of 256 references, or $PSK_LOCALITY=0). Any pointer may be NULL. */
 psk_status psk_db_locality(psk_db* db, uint32_t* slot_of, uint32_t* n_groups, uint32_t* is_identity);
+/* Measurement: the layout of the database's blocked seed index (the index the all-vs-all join walks), as it stands: *bits = width of a block's bucket table (2^bits
+ * buckets), *shift = k-mer bits below the bucket (2k - bits), *tagged = 1 when the buckets are fine enough for the walks of the all-vs-all join to match an entry by the
+ * k-mer's low byte in its value and read no key (8 bytes per visited entry instead of 12). Builds nothing: all zero until a query has built the index. Any pointer may be
+ * NULL. Added after ABI 7 without raising it: a binding detects it by its presence. */
+psk_status psk_db_seed_index_info(psk_db* db, int* bits, int* shift, int* tagged);
+/* The bucket rule behind it, on the host alone (exposed for tests): for k-mers of 2k bits, a largest block of max_block entries, n_blocks blocks and n_entries entries
+ * in all, the bucket-table width and whether the index is tagged. mode: 1 forces tagging, 0 forbids it ($PSK_BSI_TAG), anything else lets the sizes decide: tagged
+ * when the bucket tables of max(today's width, 2k - 8) bits are no larger than the 4-byte key array the walks stop reading. Tagged implies 2k - *bits <= 8. */
+void psk_bsi_plan(int k, uint64_t max_block, uint32_t n_blocks, uint64_t n_entries, int mode, int* bits, int* tagged);
 
 /* check_markers_quickly(query, ref_i, screen_val, rescue_small) for every ref of the db.
  * pass[i] in {0,1}; shared[i] = |markers(q) ∩ markers(ref_i)| (may be NULL). */

@@ -489,6 +489,16 @@ psk_status psk_db_locality(psk_db* db, uint32_t* slot_of, uint32_t* n_groups, ui
     return PSK_OK;
 }
 
+psk_status psk_db_seed_index_info(psk_db* db, int* bits, int* shift, int* tagged) {
+    if (!db) { psk_set_error("db_seed_index_info: NULL database"); return PSK_EINVAL; }
+    std::shared_lock<std::shared_mutex> lk(db->rw);
+    const bool built = db->bsi_state == 1;
+    if (bits) *bits = built ? 2 * db->params.k - db->bsi_shift : 0;
+    if (shift) *shift = built ? db->bsi_shift : 0;
+    if (tagged) *tagged = built && db->bsi_tagged ? 1 : 0;
+    return PSK_OK;
+}
+
 psk_status psk_screen(psk_db* db, const psk_sketch* q, double screen_val, int rescue_small, uint8_t* pass, uint32_t* shared) {
     if (!db || !q || !pass) { psk_set_error("screen: NULL argument"); return PSK_EINVAL; }
     PSK_LANE(lg, db->ctx);

@@ -225,7 +225,7 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
         GA.blk_tab = d_btab; GA.blk_cnt = d_bcnt; GA.blk_cap = bcap;
         if (gsl) {
             GL.bq = L.bq; GL.n_entries = L.n_bq; GL.tab = L.gsl_tab; GL.n_tab = L.gsl_n_tab; GL.ebase = L.gsl_ebase; GL.pass = L.d_pass; GL.n_refs = L.n_refs; GL.qd = d_qd;
-            GL.g_key = L.g_key; GL.g_val = L.g_val; GL.g_bucket = L.g_bucket; GL.g_shift = L.g_shift; GL.g_nb1 = L.g_nb1; GL.g_blocks = L.g_blocks; GL.g_base = L.g_base; GL.blk_tab = d_btab; GL.blk_cnt = d_bcnt; GL.blk_cap = bcap; GL.cnt = L.gsl_cnt; GL.rec = L.gsl_rec; GL.bm = L.gsl_bm; GL.un = L.gsl_un; GL.n_slices = L.gsl_n_slices;
+            GL.g_key = L.g_key; GL.g_val = L.g_val; GL.g_bucket = L.g_bucket; GL.g_shift = L.g_shift; GL.tagged = L.g_tagged; GL.g_nb1 = L.g_nb1; GL.g_blocks = L.g_blocks; GL.g_base = L.g_base; GL.blk_tab = d_btab; GL.blk_cnt = d_bcnt; GL.blk_cap = bcap; GL.cnt = L.gsl_cnt; GL.rec = L.gsl_rec; GL.bm = L.gsl_bm; GL.un = L.gsl_un; GL.n_slices = L.gsl_n_slices;
             GL.pair_cnt = L.big_list; GL.pstart = L.pstart; GL.cap = (uint32_t)cap; GL.err = L.misc; GL.p_cap = L.p_cap; GL.chunks = L.chunks; GL.n_chunks = L.nch; GL.row_q0 = L.row_q0;
             PSK_HIP(hipMemsetAsync(L.big_list, 0, 4 * ((size_t)n_pairs + 1), st));      // the slices of a pair add their counts
             PSK_TRY(gsl_count_launch(GL, st));

@@ -510,11 +510,16 @@ struct psk_db {
     // relatives - 93 of 147 entries per lookup at 10 000 genomes. A query's passing references are few and usually neighbours in insertion order: walking only the
     // blocks that hold one of them leaves 256 x 0.01 = 2.4 chance entries per lookup whatever the database size.
     int bsi_state = 0;      // 0 = not built, 1 = built, 2 = this database cannot have one
-    // Entries carry BLOCK-LOCAL reference ids (bsi_val = local ref << 48 | contig << 33 | pos << 1 | (fwd < rc), local ref = reference & 255) and the bucket tables offsets
-    // WITHIN their block (block b's entries start at bsi_base[b], a 64-bit offset): the number of references and the seeds of the database are bounded by memory only
-    // (12 bytes per seed); a block of 256 references must stay below 2^31 seeds (one radix sort), a reference below 32 768 contigs.
+    // Entries carry BLOCK-LOCAL reference ids (bsi_val = tag << 56 | local ref << 48 | contig << 33 | pos << 1 | (fwd < rc), local ref = reference & 255, tag = k-mer & 255;
+    // every reader masks the reference id to its 8 bits) and the bucket tables offsets WITHIN their block (block b's entries start at bsi_base[b], a 64-bit offset): the
+    // number of references and the seeds of the database are bounded by memory only (12 bytes per seed); a block of 256 references must stay below 2^31
+    // seeds (one radix sort), a reference below 32 768 contigs.
+    // A TAGGED index (bsi_tagged; seed_index.hip psk_bsi_plan decides) has bsi_shift <= 8: the k-mer bits below the bucket all lie in the tag, so an entry matches a k-mer
+    // exactly when it is in the k-mer's bucket and its tag is the k-mer's low byte. The slice join's walks then read no bsi_key (the contig join and the blocked prefilter
+    // still do: it stays resident). The tag byte is written always.
     PoolScratch bsi_key, bsi_val, bsi_bucket, bsi_base;
     uint64_t bsi_n = 0; int bsi_shift = 0; uint32_t bsi_nb1 = 0, bsi_blocks = 0;      // nb1 = bucket-table entries per block (2^bits + 1)
+    bool bsi_tagged = false;
     // the one-launch-sequence query (small_query.hip): 1 = every device table it reads is up to date, 2 = this database cannot take it; reset when references are added
     std::atomic<int> small_state{0};
     // the locality order (locality.hip): slot s of the seed indexes, the descriptor table of the many-query path and the columns of its pass matrix holds reference
@@ -527,7 +532,7 @@ struct psk_db {
     PoolScratch d_ref_of, d_slot_of, d_refdesc_slot;      // d_refdesc_slot: the descriptor table in slot order (d_refdesc stays in insertion order: the one-launch-sequence query reads it)
     void stale() {      // references were added: every device table and the order go
         tables_dirty = true; inv_dirty = true; desc_dirty = true; small_state = 0; gsi_key.release(); gsi_val.release(); gsi_bucket.release(); gsi_state = 0;
-        bsi_key.release(); bsi_val.release(); bsi_bucket.release(); bsi_base.release(); bsi_state = 0;
+        bsi_key.release(); bsi_val.release(); bsi_bucket.release(); bsi_base.release(); bsi_state = 0; bsi_tagged = false;
         loc_state = 0;
     }
 };

@@ -633,7 +633,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                         if (lrc == PSK_ENOMEM) { J.refit = true; ctx->dev->rr_refit++; return PSK_OK; }
                         PSK_TRY(lrc);
                         L.rows_pair_max = (uint32_t)std::min<uint64_t>(J.rows_pair_max, 0xFFFFFFFFu);
-                        L.g_key = (const uint32_t*)db->bsi_key.p; L.g_val = (const unsigned long long*)db->bsi_val.p; L.g_bucket = (const uint32_t*)db->bsi_bucket.p; L.g_shift = db->bsi_shift; L.g_nb1 = db->bsi_nb1; L.g_blocks = db->bsi_blocks; L.g_base = (const unsigned long long*)db->bsi_base.p;
+                        L.g_key = (const uint32_t*)db->bsi_key.p; L.g_val = (const unsigned long long*)db->bsi_val.p; L.g_bucket = (const uint32_t*)db->bsi_bucket.p; L.g_shift = db->bsi_shift; L.g_nb1 = db->bsi_nb1; L.g_blocks = db->bsi_blocks; L.g_base = (const unsigned long long*)db->bsi_base.p; L.g_tagged = db->bsi_tagged;
                         L.d_pass = d_pass; L.n_refs = n; L.n_bq = (uint32_t)J.bqs.size();
                         uint32_t pm = 1; for (const BatchQ& e : J.bqs) pm = std::max(pm, e.rank_hi - e.rank_lo);
                         L.p_cap = (pm + 15u) & ~15u;
@@ -793,7 +793,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                 psk_status lrc = chain_layout(ctx, n_pairs, (size_t)items, (size_t)rows, bqs.size(), &L);
                 L.rows_pair_max = (uint32_t)std::min<uint64_t>(rows_pair_max, 0xFFFFFFFFu);
                 if (round_gsi) {
-                    if (round_slice) { L.g_key = (const uint32_t*)db->bsi_key.p; L.g_val = (const unsigned long long*)db->bsi_val.p; L.g_bucket = (const uint32_t*)db->bsi_bucket.p; L.g_shift = db->bsi_shift; L.g_nb1 = db->bsi_nb1; L.g_blocks = db->bsi_blocks; L.g_base = (const unsigned long long*)db->bsi_base.p; }
+                    if (round_slice) { L.g_key = (const uint32_t*)db->bsi_key.p; L.g_val = (const unsigned long long*)db->bsi_val.p; L.g_bucket = (const uint32_t*)db->bsi_bucket.p; L.g_shift = db->bsi_shift; L.g_nb1 = db->bsi_nb1; L.g_blocks = db->bsi_blocks; L.g_base = (const unsigned long long*)db->bsi_base.p; L.g_tagged = db->bsi_tagged; }
                     else {
                         if (db->gsi_state == 1) { L.g_key = (const uint32_t*)db->gsi_key.p; L.g_val = (const unsigned long long*)db->gsi_val.p; L.g_bucket = (const uint32_t*)db->gsi_bucket.p; L.g_shift = db->gsi_shift; }
                         if (round_bsi) { L.b_key = (const uint32_t*)db->bsi_key.p; L.b_val = (const unsigned long long*)db->bsi_val.p; L.b_bucket = (const uint32_t*)db->bsi_bucket.p; L.b_shift = db->bsi_shift; L.b_nb1 = db->bsi_nb1; L.b_blocks = db->bsi_blocks; L.b_base = (const unsigned long long*)db->bsi_base.p; L.b_max = (uint32_t)std::max(1.0, max_blocks_join); }

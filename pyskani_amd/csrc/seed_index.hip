@@ -5,14 +5,17 @@
 
 // ------------------------------------------------------------------ database-wide seed index (psk_db::gsi_*)
 struct GsiSeg { const uint32_t* kmer; const uint64_t* pm; uint32_t n, off; };
+// TAG (the blocked index, whose reference ids are 8 bits): the k-mer's low byte goes into the value's bits 56..63 (common.h: psk_db::bsi_val)
+template <bool TAG>
 __global__ __launch_bounds__(256) void gsi_gather_kernel(const GsiSeg* __restrict__ segs, uint32_t* __restrict__ key, unsigned long long* __restrict__ val) {
     const GsiSeg sg = segs[blockIdx.y];
     const unsigned long long ref = (unsigned long long)blockIdx.y << 48;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < sg.n; i += gridDim.x * blockDim.x) {
         const unsigned long long pm = sg.pm[i];
         const uint32_t meta = (uint32_t)pm;      // contig << 1 | (fwd < rc)
-        key[sg.off + i] = sg.kmer[i];
-        val[sg.off + i] = ref | ((unsigned long long)(meta >> 1) << 33) | ((pm >> 32) << 1) | (meta & 1u);
+        const uint32_t km = sg.kmer[i];
+        key[sg.off + i] = km;
+        val[sg.off + i] = (TAG ? (unsigned long long)(km & 0xFFu) << 56 : 0ull) | ref | ((unsigned long long)(meta >> 1) << 33) | ((pm >> 32) << 1) | (meta & 1u);
     }
 }
 // bucket[b] = first entry whose k-mer >> shift is >= b (b = 0 .. nb)
@@ -66,7 +69,7 @@ psk_status build_gsi(Lane* ctx, psk_db* db) {
     };
     hipError_t e = hipMemcpyAsync(T + o_s, segs.data(), sizeof(GsiSeg) * (size_t)n, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return fail(e, "gsi: upload");
-    hipLaunchKernelGGL(gsi_gather_kernel, dim3(std::max(1u, std::min(64u, (maxn + 4095u) / 4096u)), n), dim3(256), 0, st, (const GsiSeg*)(T + o_s), (uint32_t*)(T + o_k), (unsigned long long*)(T + o_v));
+    hipLaunchKernelGGL(gsi_gather_kernel<false>, dim3(std::max(1u, std::min(64u, (maxn + 4095u) / 4096u)), n), dim3(256), 0, st, (const GsiSeg*)(T + o_s), (uint32_t*)(T + o_k), (unsigned long long*)(T + o_v));
     e = hipcub::DeviceRadixSort::SortPairs(T + o_t, ts, (const uint32_t*)(T + o_k), (uint32_t*)db->gsi_key.p, (const unsigned long long*)(T + o_v), (unsigned long long*)db->gsi_val.p, (int)N, 0, kbits, st);
     if (e != hipSuccess) return fail(e, "gsi: sort");
     hipLaunchKernelGGL(gsi_bucket_kernel, dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, st, (const uint32_t*)db->gsi_key.p, (uint32_t)N, kbits - bits, nb, (uint32_t*)db->gsi_bucket.p);
@@ -87,6 +90,20 @@ __global__ __launch_bounds__(256) void bsi_bucket_kernel(const uint32_t* __restr
     const uint32_t from = i ? (key[i - 1] >> shift) + 1u : 0u;
     for (uint32_t x = from; x <= b; x++) bucket[x] = base + i;
     if (i == n - 1) for (uint32_t x = b + 1; x <= nb; x++) bucket[x] = base + n;
+}
+// The bucket rule of the blocked index (no GPU; exported for the tests). bits0: ~8 entries per bucket of the largest block. A TAGGED index has buckets fine enough
+// that the k-mer bits below the bucket fit the value's tag byte (shift = 2k - bits <= 8): an entry then matches a k-mer exactly when it lies in the k-mer's bucket and
+// carries its low byte, and the walks read no key. mode 1 forces, 0 forbids ($PSK_BSI_TAG); otherwise the index is tagged when the finer bucket tables are no larger
+// than the key array the walks stop reading. An untagged index keeps bits0.
+void psk_bsi_plan(int k, uint64_t max_block, uint32_t n_blocks, uint64_t n_entries, int mode, int* bits, int* tagged) {
+    const int kbits = 2 * k;
+    int bits0 = 4; while (bits0 < 24 && (8ull << bits0) < max_block) bits0++;
+    if (bits0 > kbits) bits0 = kbits;
+    const int bits1 = std::max(bits0, kbits - 8);
+    bool tag = false;
+    if (k >= 1 && k <= 16 && mode != 0) tag = mode == 1 || (uint64_t)n_blocks * ((1ull << bits1) + 1ull) * 4ull <= 4ull * n_entries;
+    if (bits) *bits = tag ? bits1 : bits0;
+    if (tagged) *tagged = tag ? 1 : 0;
 }
 // called with the database locked exclusively; leaves bsi_state 1 (built) or 2 (this database cannot have one)
 psk_status build_bsi(Lane* ctx, psk_db* db) {
@@ -118,8 +135,8 @@ psk_status build_bsi(Lane* ctx, psk_db* db) {
     base[n_blocks] = N;
     if (N == 0) return PSK_OK;
     const int kbits = 2 * db->params.k;
-    int bits = 4; while (bits < 24 && (8ull << bits) < max_block) bits++;      // ~8 entries per bucket of the largest block
-    if (bits > kbits) bits = kbits;
+    int bits = 0, tagged = 0;
+    psk_bsi_plan(db->params.k, max_block, n_blocks, N, env_val("PSK_BSI_TAG").force(), &bits, &tagged);
     const uint32_t nb = 1u << bits;
     size_t ts = 0;
     PSK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, ts, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)max_block, 0, kbits, st));
@@ -146,7 +163,7 @@ psk_status build_bsi(Lane* ctx, psk_db* db) {
         const uint32_t r0 = b << BSI_BLOG, r1 = std::min<uint32_t>(n, (b + 1) << BSI_BLOG);
         const size_t o = (size_t)base[b]; const uint32_t cnt = (uint32_t)(base[b + 1] - base[b]);
         if (cnt) {
-            hipLaunchKernelGGL(gsi_gather_kernel, dim3(std::max(1u, std::min(64u, (maxn + 4095u) / 4096u)), r1 - r0), dim3(256), 0, st, (const GsiSeg*)(T + o_s) + r0, (uint32_t*)(T + o_k), (unsigned long long*)(T + o_v));
+            hipLaunchKernelGGL(gsi_gather_kernel<true>, dim3(std::max(1u, std::min(64u, (maxn + 4095u) / 4096u)), r1 - r0), dim3(256), 0, st, (const GsiSeg*)(T + o_s) + r0, (uint32_t*)(T + o_k), (unsigned long long*)(T + o_v));
             size_t ts_b = ts;
             e = hipcub::DeviceRadixSort::SortPairs(T + o_t, ts_b, (const uint32_t*)(T + o_k), (uint32_t*)db->bsi_key.p + o, (const unsigned long long*)(T + o_v), (unsigned long long*)db->bsi_val.p + o, (int)cnt, 0, kbits, st);
             if (e != hipSuccess) return fail(e, "bsi: sort");
@@ -155,7 +172,7 @@ psk_status build_bsi(Lane* ctx, psk_db* db) {
     }
     e = hipStreamSynchronize(st);      // (segs, base and tmp die with this frame)
     if (e != hipSuccess) return fail(e, "bsi: build");
-    db->bsi_n = N; db->bsi_shift = kbits - bits; db->bsi_nb1 = nb + 1; db->bsi_blocks = n_blocks;
+    db->bsi_n = N; db->bsi_shift = kbits - bits; db->bsi_nb1 = nb + 1; db->bsi_blocks = n_blocks; db->bsi_tagged = tagged != 0;
     db->bsi_state = 1;
     return PSK_OK;
 }

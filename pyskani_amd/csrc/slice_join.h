@@ -24,6 +24,7 @@ struct GslArgs {
     uint32_t* un; uint32_t n_slices;        // per (entry, slice) GSL_WORDS words: the seeds that head a chunk of some pair of the entry (heads kernel; zeroed by its launcher)
     const uint8_t* pass; uint32_t n_refs; const SketchDesc* qd;
     const uint32_t* g_key; const unsigned long long* g_val; const uint32_t* g_bucket; int g_shift;      // psk_db::bsi_*: the seed index in blocks of 2^BSI_BLOG references
+    bool tagged;                            // a tagged index (psk_db::bsi_tagged): the walks test an entry's tag and read no g_key
     const unsigned long long* g_base;       // first entry of every block (the bucket tables hold offsets within their block)
     uint32_t g_nb1, g_blocks;               // bucket-table entries per block; blocks
     uint32_t* blk_tab; uint32_t* blk_cnt; uint32_t blk_cap;      // per entry: the index blocks that hold one of its pairs' references (gsl_blocks_kernel): blk_cnt[e] rows of GSL_BT_WORDS words at blk_tab[e * blk_cap * GSL_BT_WORDS]

@@ -63,7 +63,12 @@ static size_t gsl_walk_lds(const GslArgs& A, bool emit) {
 
 // (streaming - nontemporal - stores of the anchors were measured on the 10 000 x 10 000 step: the walk takes the same time and the DP kernel that reads the anchors next 178 instead of
 // 165 ms: plain stores; profiles/r5/r5_ablation.md)
-template <bool EMIT>
+// TAGGED: a tagged index (psk_db::bsi_tagged) - the walk reads an entry's value alone and the match is "in the k-mer's bucket and tag == the k-mer's low byte"; otherwise key
+// and value, and the match is key == k-mer. The accessors below are all the loop knows of a value's top 16 bits (tag << 8 | local reference).
+__device__ __forceinline__ uint32_t gsl_ref_word(unsigned long long v) { return (uint32_t)(v >> 53) & 7u; }      // the local reference's group of 32
+__device__ __forceinline__ uint32_t gsl_ref_bit(unsigned long long v) { return (uint32_t)(v >> 48) & 31u; }      // ... and its bit within the group
+__device__ __forceinline__ uint32_t gsl_tag(unsigned long long v) { return (uint32_t)(v >> 56); }
+template <bool EMIT, bool TAGGED>
 __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
     extern __shared__ uint4 s_gsl[];
     const int lane = threadIdx.x;
@@ -111,7 +116,7 @@ __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
     {
     const uint32_t blk = brow[8];
     const unsigned long long x_base = ((unsigned long long)brow[11] << 32) | brow[10];
-    const uint32_t* __restrict__ x_key = A.g_key + x_base; const unsigned long long* __restrict__ x_val = A.g_val + x_base;
+    const uint32_t* __restrict__ x_key = A.g_key + x_base; const unsigned long long* __restrict__ x_val = A.g_val + x_base;      // (x_key: read by the untagged walk alone)
     {   // the block's 256 references of the pass row -> eight (32 bits, passing references before them) entries: reference -> pair of the entry in ONE 8-byte LDS read
         lds_wave_sync();      // (the previous block's last lookups are through)
         if (lane < 8) {
@@ -149,7 +154,7 @@ __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
                 ns[u] = 63u - (uint32_t)__clzll((long long)own); \
                 nx[u] = (uint32_t)__builtin_amdgcn_readlane((int)lo, (int)ns[u]) + 64u * ((t) - (uint32_t)__builtin_amdgcn_readlane((int)pre, (int)ns[u])); \
                 nh[u] = (uint32_t)__builtin_amdgcn_readlane((int)hi, (int)ns[u]); \
-                if (nx[u] + (uint32_t)lane < nh[u]) { nk[u] = x_key[nx[u] + lane]; nv[u] = x_val[nx[u] + lane]; } \
+                if (nx[u] + (uint32_t)lane < nh[u]) { if (!TAGGED) nk[u] = x_key[nx[u] + lane]; nv[u] = x_val[nx[u] + lane]; } \
             } } while (0)
 #pragma unroll
         for (uint32_t u = 0; u < GSL_AHEAD; u++) GSL_FETCH(u, u);
@@ -163,12 +168,14 @@ __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
             // what is sequential - a pair's cursor - is only in the second part
             uint32_t slots[GSL_AHEAD]; uint2 bps[GSL_AHEAD];
 #pragma unroll
-            for (uint32_t u = 0; u < GSL_AHEAD; u++) bps[u] = s_bp[(uint32_t)(cv[u] >> 53) & 7u];      // (every lane reads: a lane without an entry has v = 0 - the block's first word; an entry's reference is of this block)
+            for (uint32_t u = 0; u < GSL_AHEAD; u++) bps[u] = s_bp[gsl_ref_word(cv[u])];      // (every lane reads: a lane without an entry has v = 0 - the block's first word; an entry's reference is of this block)
 #pragma unroll
             for (uint32_t u = 0; u < GSL_AHEAD; u++) {
                 const uint32_t skm = (uint32_t)__builtin_amdgcn_readlane((int)km, (int)cs[u]);
-                const uint32_t b = (uint32_t)(cv[u] >> 48) & 31u, rk = bps[u].y + (uint32_t)__popc(bps[u].x & ~(~0u << b)) - B.rank_lo;
-                const bool ok = cx[u] + (uint32_t)lane < ch[u] && ck[u] == skm && ((bps[u].x >> b) & 1u) && rk < P;      // (steps past the batch's last: nk = 0xFFFFFFFF is no k-mer, nh = 0)
+                const uint32_t b = gsl_ref_bit(cv[u]), rk = bps[u].y + (uint32_t)__popc(bps[u].x & ~(~0u << b)) - B.rank_lo;
+                // (a tagged index: the bucket holds the k-mers that agree with the seed's above bit g_shift <= 8, the tag tells the rest. Steps past the batch's last: nh = 0, no lane is in range; nk = 0xFFFFFFFF is no k-mer)
+                const bool hit = TAGGED ? gsl_tag(cv[u]) == (skm & 0xFFu) : ck[u] == skm;
+                const bool ok = cx[u] + (uint32_t)lane < ch[u] && hit && ((bps[u].x >> b) & 1u) && rk < P;
                 slots[u] = ok ? rk : 0xFFFFFFFFu;
             }
 #pragma unroll
@@ -431,7 +438,8 @@ psk_status gsl_blocks_launch(const BatchQ* bq, uint32_t n_entries, const uint8_t
     return PSK_OK;
 }
 psk_status gsl_count_launch(const GslArgs& A, hipStream_t st) {
-    hipLaunchKernelGGL(gsl_walk_kernel<false>, dim3(A.n_tab), dim3(64), gsl_walk_lds(A, false), st, A);
+    auto* const walk = A.tagged ? gsl_walk_kernel<false, true> : gsl_walk_kernel<false, false>;
+    hipLaunchKernelGGL(walk, dim3(A.n_tab), dim3(64), gsl_walk_lds(A, false), st, A);
     PSK_HIP(hipGetLastError());
     return PSK_OK;
 }
@@ -442,7 +450,8 @@ psk_status gsl_heads_launch(const GslArgs& A, hipStream_t st) {
     return PSK_OK;
 }
 psk_status gsl_emit_launch(const GslArgs& A, hipStream_t st) {
-    hipLaunchKernelGGL(gsl_walk_kernel<true>, dim3(A.n_tab), dim3(64), gsl_walk_lds(A, true), st, A);
+    auto* const walk = A.tagged ? gsl_walk_kernel<true, true> : gsl_walk_kernel<true, false>;
+    hipLaunchKernelGGL(walk, dim3(A.n_tab), dim3(64), gsl_walk_lds(A, true), st, A);
     PSK_HIP(hipGetLastError());
     return PSK_OK;
 }

@@ -142,6 +142,9 @@ extern "C" {
     pub fn psk_ctx_cluster_stats(ctx: *mut PskCtx, edges: *mut u64, rounds: *mut u64, hook_passes: *mut u64) -> c_int;
     // the locality order of the references (slot_of: psk_db_size entries or null)
     pub fn psk_db_locality(db: *mut PskDb, slot_of: *mut u32, n_groups: *mut u32, is_identity: *mut u32) -> c_int;
+    // the blocked seed index's layout as it stands (zeros before a query has built it), and the host-side bucket rule behind it
+    pub fn psk_db_seed_index_info(db: *mut PskDb, bits: *mut c_int, shift: *mut c_int, tagged: *mut c_int) -> c_int;
+    pub fn psk_bsi_plan(k: c_int, max_block: u64, n_blocks: u32, n_entries: u64, mode: c_int, bits: *mut c_int, tagged: *mut c_int);
     // the two halves of `query`, for a disk-backed Database (markers resident, sketches loaded per query)
     pub fn psk_screen(db: *mut PskDb, q: *const PskSketch, screen_val: f64, rescue_small: c_int,
                       pass: *mut u8, shared: *mut u32) -> c_int;
