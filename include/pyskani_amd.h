@@ -103,7 +103,7 @@ const char* psk_version(void);
 /* The C-ABI's revision: raised whenever an entry point's parameters or a structure's layout change (4: psk_sketch_unpack takes the extent of its source buffer as third
  * argument; 5: psk_hit_min / psk_query_many_min / psk_gather_hits_min / psk_ctx_join_work added;
  * 6: psk_db_locality added; 7: psk_ctx_rerun_stats added). psk_query_many_tri and psk_query_many_tri_min came after 7 WITHOUT raising it: no existing argument
- * list or structure moved, and a binding that wants them detects them by their presence (dlsym); psk_cluster_records, psk_ctx_cluster_stats and psk_ctx_tier_stats likewise. A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
+ * list or structure moved, and a binding that wants them detects them by their presence (dlsym); psk_cluster_records, psk_ctx_cluster_stats, psk_ctx_tier_stats, psk_cluster_forest and psk_ctx_forest_stats likewise. A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
  * written against before it calls anything else: an argument list that moved is a memory error, not a link error. */
 #define PSK_ABI_VERSION 7
 int psk_abi_version(void);
@@ -364,6 +364,38 @@ psk_status psk_cluster_records(psk_ctx* ctx, const psk_hit_min* recs, uint64_t n
 /* Measurement: the context's last psk_cluster_records call that reached the device - undirected edges of its graph, greedy rounds that decided a vertex (linkage 0),
  * hook passes that joined two labels (linkage 1). Any pointer may be NULL. */
 psk_status psk_ctx_cluster_stats(psk_ctx* ctx, uint64_t* edges, uint64_t* rounds, uint64_t* hook_passes);
+
+/* ---- the linkage forest: the maximum spanning forest of the same ANI graph (csrc/cluster.hip). Its edges in descending weight are the merge sequence of single-linkage
+ * agglomeration, and dropping the edges below t leaves exactly the single-linkage clusters at t: one call answers every cut from its floor up.
+ * Edges
+ *  - Records, qualification, edges and weights are exactly those of psk_cluster_records. q = query & 0x7FFFFFFF, r = ref_index.
+ *  - A record qualifies iff q != r, ani >= (float)min_ani and the aligned-fraction rule holds. All comparisons are in float. A NaN fails.
+ *  - The unordered pair is an edge iff one of its records qualifies. Its weight is the largest qualifying ani.
+ *  - psk_cluster_opts is reused with its defaults (min_ani <= 0: 0.95, min_af < 0: 0.5, min_af == 0: no fraction rule).
+ *  - linkage must be 0 or 1 and is otherwise ignored.
+ *  - Here min_ani is the FLOOR: the lowest cut the forest can later answer.
+ * Edge order
+ *  - Write an edge as (a, b, w) with a < b.
+ *  - Edge e PRECEDES f iff w_e > w_f, or the weights are bit-equal and (a_e, b_e) < (a_f, b_f) lexicographically.
+ *  - This is a strict total order. Edges are deduplicated, so no two share (a, b).
+ * The forest
+ *  - Walk the edges in that order and keep an edge iff its ends are not yet connected (Kruskal). The edges kept are the forest.
+ *  - Under a strict total order the forest is unique. Any correct parallel algorithm returns the same set.
+ * Output
+ *  - The forest's edges IN THAT ORDER, as three host arrays edge_a[], edge_b[] (with a < b) and edge_ani[].
+ *  - edge_ani[] holds the input's float bits. It is never computed.
+ *  - Also *n_edges = n_genomes - components.
+ *  - The caller provides room for n_genomes - 1 entries each. NULL arrays are allowed when n_genomes <= 1.
+ * Refusals and limits
+ *  - These are as in psk_cluster_records.
+ *  - An index >= n_genomes is PSK_EINVAL with the same message shape, and the context stays usable.
+ *  - n_recs >= 2^30 or n_genomes >= 2^31 is PSK_ELIMIT.
+ *  - n_recs == 0 gives *n_edges = 0 without a device call. */
+psk_status psk_cluster_forest(psk_ctx* ctx, const psk_hit_min* recs, uint64_t n_recs, uint32_t n_genomes,
+                              const psk_cluster_opts* opts, uint32_t* edge_a, uint32_t* edge_b, float* edge_ani, uint32_t* n_edges);
+/* Measurement: the context's last psk_cluster_forest call that reached the device - undirected edges of its graph, Boruvka rounds that hooked at least one component,
+ * pointer-jump launches (those that found something left to do; the launches behind them return at once). Any pointer may be NULL. */
+psk_status psk_ctx_forest_stats(psk_ctx* ctx, uint64_t* edges, uint64_t* rounds, uint64_t* jump_passes);
 
 #ifdef __cplusplus
 }

@@ -62,7 +62,7 @@ SYMBOLS = [
     "psk_ctx_synchronize", "psk_pack2bit_host", "psk_ctx_small_query_stats", "psk_ctx_rerun_stats", "psk_ctx_tier_stats", "psk_ctx_set_timing", "psk_ctx_timing", "psk_db_add_batch", "psk_device_alloc", "psk_device_free", "psk_memcpy_h2d",
     "psk_sketch_host", "psk_sketch_many_host", "psk_sketch_batch_device", "psk_sketch_free", "psk_sketch_free_many", "psk_sketch_info",
     "psk_sketch_export", "psk_sketch_contig_lens", "psk_sketch_import", "psk_db_create", "psk_db_destroy", "psk_db_add", "psk_db_size",
-    "psk_db_name", "psk_db_sketch", "psk_db_locality", "psk_db_seed_index_info", "psk_bsi_plan", "psk_screen", "psk_chain", "psk_query", "psk_query_host", "psk_query_many", "psk_query_many_min", "psk_query_many_tri", "psk_query_many_tri_min", "psk_cluster_records", "psk_ctx_cluster_stats", "psk_gather_hits_min",
+    "psk_db_name", "psk_db_sketch", "psk_db_locality", "psk_db_seed_index_info", "psk_bsi_plan", "psk_screen", "psk_chain", "psk_query", "psk_query_host", "psk_query_many", "psk_query_many_min", "psk_query_many_tri", "psk_query_many_tri_min", "psk_cluster_records", "psk_ctx_cluster_stats", "psk_cluster_forest", "psk_ctx_forest_stats", "psk_gather_hits_min",
     "psk_sketch_pack_size", "psk_sketch_pack", "psk_sketch_unpack", "psk_sketch_pack_many", "psk_ctx_clock_probe", "psk_ctx_work", "psk_ctx_join_work",
     "psk_comm_unique_id", "psk_comm_create", "psk_comm_destroy", "psk_comm_info", "psk_gather_hits", "psk_gather_sketches",
     "psk_model_create", "psk_model_load_json", "psk_model_load_file", "psk_model_free", "psk_model_info", "psk_model_predict",
@@ -140,6 +140,8 @@ def load():
     lib.psk_query_many_tri_min.argtypes = [vp, C.POINTER(vp), u32, C.POINTER(C.c_int64), u64, C.POINTER(QueryOpts), C.POINTER(C.POINTER(HitMin)), C.POINTER(u64)]
     lib.psk_cluster_records.argtypes = [vp, vp, u64, u32, vp, C.POINTER(ClusterOpts), vp, vp, C.POINTER(u32)]
     lib.psk_ctx_cluster_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    lib.psk_cluster_forest.argtypes = [vp, vp, u64, u32, C.POINTER(ClusterOpts), vp, vp, vp, C.POINTER(u32)]
+    lib.psk_ctx_forest_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     lib.psk_gather_hits_min.argtypes = [vp, vp, u64, C.POINTER(C.POINTER(HitMin)), C.POINTER(u64), C.POINTER(u64)]
     lib.psk_sketch_pack_size.argtypes = [vp, C.POINTER(u64)]
     lib.psk_sketch_pack.argtypes = [vp, vp, u64]

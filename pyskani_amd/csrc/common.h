@@ -118,6 +118,8 @@ struct psk_ctx {
     std::atomic<uint64_t> tier[TIER_COUNT] = {};
     // the cluster stage's last call (cluster.hip; psk_ctx_cluster_stats): undirected edges, greedy rounds that decided a vertex, hook passes of single linkage
     std::atomic<uint64_t> cl_edges{0}, cl_rounds{0}, cl_hooks{0};
+    // the linkage forest's last call that reached the device (cluster.hip; psk_ctx_forest_stats): undirected edges, rounds that hooked a component, pointer-jump launches
+    std::atomic<uint64_t> fo_edges{0}, fo_rounds{0}, fo_jumps{0};
     // lanes: created on demand, at most max_lanes; a call takes a free one (LaneGuard) and gives it back
     std::mutex lanes_mu;
     std::condition_variable lanes_cv;

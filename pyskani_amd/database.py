@@ -758,6 +758,16 @@ class Database:
         rep_of, rep_ani = cluster_records(recs, n, min_ani=min_ani, min_af=min_af, af=af, linkage=linkage, priority=priority, device=self._device)
         return Dereplication(rep_of, rep_ani, list(self._names), priority)
 
+    def linkage_forest(self, *, min_ani=0.80, min_af=0.5, af="both", learned_ani=None, median=False, robust=False, cutoff=None, faster_small=False):
+        """The single-linkage tree of the database's own all-vs-all: `triangle_records`, then `forest_records` (whose docstring gives the rule), as a `Forest` with
+        `names` filled. One call answers every cut from the floor `min_ani` up (`Forest.labels`) and gives the merge order (`Forest.merges`, `Forest.newick`). The
+        restrictions of `triangle_records` hold: a memory-resident database, no name sketched twice."""
+        _cluster_args(af, "single")
+        recs, _ = self.triangle_records(learned_ani=learned_ani, median=median, robust=robust, cutoff=cutoff, faster_small=faster_small)
+        f = forest_records(recs, len(self._names), min_ani=min_ani, min_af=min_af, af=af, device=self._device)
+        f.names = list(self._names)
+        return f
+
     def triangle(self, *, learned_ani=None, median=False, robust=False, cutoff=None, faster_small=False):
         """`triangle_records` as a list of `Hit` lists indexed by insertion index: entry i holds genome i's hits against the genomes added after it."""
         recs, offs = self.triangle_records(learned_ani=learned_ani, median=median, robust=robust, cutoff=cutoff, faster_small=faster_small, raw=True)
@@ -902,6 +912,18 @@ def _cluster_priority(priority, n):
     return np.ascontiguousarray(prio, dtype=np.uint64)
 
 
+def _cluster_input(records, n):
+    """(contiguous records, int n) of `cluster_records` and `forest_records`, or ValueError"""
+    if not isinstance(records, np.ndarray) or records.dtype != Database._HIT_MIN_DTYPE:
+        raise ValueError("records must be a numpy array of psk_hit_min records (the dtype of Database.triangle_records)")
+    if records.ndim != 1:
+        raise ValueError("records must be one-dimensional")
+    n = int(n)
+    if n < 0 or n >= 1 << 31:
+        raise ValueError(f"n = {n}")
+    return np.ascontiguousarray(records), n
+
+
 def cluster_records(records, n, *, min_ani=0.95, min_af=0.5, af="both", linkage="greedy", priority=None, device=0):
     """Representatives and clusters of n genomes from the psk_hit_min records of their all-vs-all (`Database.triangle_records`, a full `query_handles` run, or the
     gathered records of a sharded run, which are the same on every rank) -> `(rep_of, rep_ani)`, uint32 and float32 arrays of n entries. Runs on the GPU
@@ -916,15 +938,8 @@ def cluster_records(records, n, *, min_ani=0.95, min_af=0.5, af="both", linkage=
     weight of the edge to its representative.
     linkage="single": connected components, represented by their first genome in the order; rep_ani = 1 for it, else the weight of the direct edge to it, 0 without one."""
     af_rule, link = _cluster_args(af, linkage)
-    if not isinstance(records, np.ndarray) or records.dtype != Database._HIT_MIN_DTYPE:
-        raise ValueError("records must be a numpy array of psk_hit_min records (the dtype of Database.triangle_records)")
-    if records.ndim != 1:
-        raise ValueError("records must be one-dimensional")
-    n = int(n)
-    if n < 0 or n >= 1 << 31:
-        raise ValueError(f"n = {n}")
+    recs, n = _cluster_input(records, n)
     prio = None if priority is None else _cluster_priority(priority, n)
-    recs = np.ascontiguousarray(records)
     lib = _capi.load()
     ctx = default_context(device)
     rep_of, rep_ani = np.empty(n, np.uint32), np.empty(n, np.float32)
@@ -954,3 +969,136 @@ class Dereplication:
 
     def __repr__(self):
         return f"Dereplication({len(self.rep_of)} genomes, {len(self.representatives)} representatives)"
+
+
+def forest_records(records, n, *, min_ani=0.80, min_af=0.5, af="both", device=0):
+    """The linkage forest of n genomes from the psk_hit_min records of their all-vs-all (the records `cluster_records` takes: `Database.triangle_records`, a full
+    `query_handles` run, or a sharded run's gathered records) -> `Forest`. Runs on the GPU (psk_cluster_forest).
+
+    Records qualify and pairs become weighted edges exactly as in `cluster_records`; `min_ani` is the FLOOR here, the lowest cut the forest can answer later. Its
+    default, 0.80, is the screen's default cutoff: pairs below it were never chained. Write an edge as (a, b, w) with a < b; edge e precedes f iff w_e > w_f, or
+    the weights are bit-equal and (a_e, b_e) < (a_f, b_f). The forest is what Kruskal keeps walking the edges in that order (the maximum spanning forest, with every
+    tie decided: a function of the records alone), and its edges come in that order - the merge sequence of single-linkage agglomeration. An index of n or more
+    raises ValueError."""
+    af_rule, _ = _cluster_args(af, "single")
+    recs, n = _cluster_input(records, n)
+    lib = _capi.load()
+    ctx = default_context(device)
+    room = max(n - 1, 0)
+    a, b, ani = np.empty(room, np.uint32), np.empty(room, np.uint32), np.empty(room, np.float32)
+    cnt = C.c_uint32(0)
+    opts = _capi.ClusterOpts(float(min_ani), float(min_af), af_rule, 1)
+    _capi.check(lib.psk_cluster_forest(ctx._h, recs.ctypes.data if len(recs) else None, len(recs), n, C.byref(opts), a.ctypes.data if room else None,
+                                       b.ctypes.data if room else None, ani.ctypes.data if room else None, C.byref(cnt)))
+    k = int(cnt.value)
+    return Forest(n, a[:k], b[:k], ani[:k], 0.95 if min_ani <= 0 else float(min_ani))
+
+
+class Forest:
+    """What `forest_records` and `Database.linkage_forest` return: the maximum spanning forest of the ANI graph. `n` genomes; `a`, `b` (a < b) and `ani`: its edges
+    in merge order (heaviest first, ties by (a, b)), read-only arrays; `min_ani`: the floor the edges were taken at; `names`: the genomes' names or None.
+    `len()` is the edge count, n - components at the floor. Everything below is host-side numpy over at most n - 1 edges."""
+
+    def __init__(self, n, a, b, ani, min_ani, names=None):
+        self.n = int(n)
+        self.a, self.b, self.ani = (np.array(x, dtype=t) for x, t in ((a, np.uint32), (b, np.uint32), (ani, np.float32)))
+        if not (self.a.ndim == 1 and len(self.a) == len(self.b) == len(self.ani)) or len(self.a) > max(self.n - 1, 0):
+            raise ValueError("a, b and ani must be one-dimensional, of one length, at most n - 1")
+        if len(self.a) and not (bool((self.a < self.b).all()) and int(self.b.max()) < self.n):
+            raise ValueError("an edge needs a < b < n")
+        for x in (self.a, self.b, self.ani):
+            x.setflags(write=False)
+        self.min_ani = float(min_ani)
+        self.names = None if names is None else list(names)
+        if self.names is not None and len(self.names) != self.n:
+            raise ValueError(f"names must hold one name per genome: {self.n} expected, {len(self.names)} given")
+
+    def __len__(self):
+        return len(self.a)
+
+    def __repr__(self):
+        return f"Forest({self.n} genomes, {len(self.a)} edges, floor {self.min_ani})"
+
+    def labels(self, min_ani):
+        """uint32[n]: label[v] = the smallest genome index of v's component among the edges with ani >= float32(min_ani) - the single-linkage clusters at that cut,
+        equal to `cluster_records(records, n, linkage="single", min_ani=min_ani, ..., priority=None)[0]` for every cut from the floor up. A cut below the floor
+        raises ValueError: the forest holds no edge from there."""
+        t = np.float32(min_ani)
+        if not bool(t >= np.float32(self.min_ani)):
+            raise ValueError(f"min_ani = {min_ani} is below the forest's floor {self.min_ani} (or no number)")
+        parent = list(range(self.n))
+        keep = self.ani >= t
+        for x, y in zip(self.a[keep].tolist(), self.b[keep].tolist()):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]; x = parent[x]
+            while parent[y] != y:
+                parent[y] = parent[parent[y]]; y = parent[y]
+            if x < y:
+                parent[y] = x
+            elif y < x:
+                parent[x] = y
+        for v in range(self.n):      # (a root is its component's smallest index: parent[v] <= v, so one ascending pass flattens)
+            parent[v] = parent[parent[v]]
+        return np.array(parent, dtype=np.uint32)
+
+    def merges(self):
+        """(Z, order): Z is a float64 (n - 1, 4) array in SciPy's linkage layout - row i joins clusters Z[i, 0] < Z[i, 1] (ids below n are genomes, n + j is row j's
+        result) at distance Z[i, 2] = 1.0 - float64(ani) into Z[i, 3] members. The forest's edges come first, in their order; the components left over are then joined
+        at distance 1.0, sorted by their smallest member: the first two, then the result with the next. `order` is the leaves from left to right (int64[n]). n <= 1
+        gives an empty (0, 4) array. `scipy.cluster.hierarchy.dendrogram(Z)` takes it as it is; SciPy is not needed here."""
+        n = self.n
+        Z = np.zeros((max(n - 1, 0), 4), np.float64)
+        parent, cid, size = list(range(n)), list(range(n)), [1] * n      # union-find whose root is the component's smallest member; the root's cluster id and size
+
+        def find(x):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]; x = parent[x]
+            return x
+
+        def join(i, x, y, d):
+            lo, hi = (x, y) if x < y else (y, x)
+            c0, c1 = (cid[x], cid[y]) if cid[x] < cid[y] else (cid[y], cid[x])
+            size[lo] += size[hi]
+            parent[hi] = lo
+            cid[lo] = n + i
+            Z[i] = (c0, c1, d, size[lo])
+            return lo
+        i = 0
+        for x, y, w in zip(self.a.tolist(), self.b.tolist(), self.ani.tolist()):
+            x, y = find(x), find(y)
+            if x == y:
+                raise ValueError("the edges hold a cycle: not a forest")
+            join(i, x, y, 1.0 - float(w))
+            i += 1
+        roots = [v for v in range(n) if parent[v] == v]      # ascending: by smallest member
+        for r in roots[1:]:
+            join(i, roots[0], r, 1.0)
+            i += 1
+        kids = {n + j: (int(Z[j, 0]), int(Z[j, 1])) for j in range(len(Z))}
+        order, stack = [], [n + len(Z) - 1] if len(Z) else list(range(n))
+        while stack:
+            c = stack.pop()
+            if c < n:
+                order.append(c)
+            else:
+                stack.extend(reversed(kids[c]))
+        return Z, np.array(order, dtype=np.int64)
+
+    def newick(self):
+        """The tree of `merges` as Newick text: leaves are `names` (indices without names), a node's height is its merge distance, a branch's length the difference
+        of heights. Built by joining strings bottom-up: for small n."""
+        n = self.n
+        if n == 0:
+            return ";"
+        Z, _ = self.merges()
+
+        def leaf(v):
+            s = str(v) if self.names is None else str(self.names[v])
+            return "'" + s.replace("'", "''") + "'" if any(ch in s for ch in " ()[]':;,\t\n") else s
+        text = {v: leaf(v) for v in range(n)}
+        height = {v: 0.0 for v in range(n)}
+        for j, (x, y, d, _) in enumerate(Z.tolist()):
+            x, y = int(x), int(y)
+            text[n + j] = f"({text.pop(x)}:{d - height[x]:.6g},{text.pop(y)}:{d - height[y]:.6g})"
+            height[n + j] = d
+        return text[n + len(Z) - 1 if len(Z) else 0] + ";"

@@ -140,6 +140,11 @@ extern "C" {
     pub fn psk_cluster_records(ctx: *mut PskCtx, recs: *const PskHitMin, n_recs: u64, n_genomes: u32, priority: *const u64, opts: *const PskClusterOpts,
                                rep_of: *mut u32, rep_ani: *mut f32, n_reps: *mut u32) -> c_int;
     pub fn psk_ctx_cluster_stats(ctx: *mut PskCtx, edges: *mut u64, rounds: *mut u64, hook_passes: *mut u64) -> c_int;
+    // the linkage forest: the maximum spanning forest of the same graph, its edges in merge order (room for n_genomes - 1 entries in each array). Added after
+    // PSK_ABI_VERSION 7 without raising it as well
+    pub fn psk_cluster_forest(ctx: *mut PskCtx, recs: *const PskHitMin, n_recs: u64, n_genomes: u32, opts: *const PskClusterOpts,
+                              edge_a: *mut u32, edge_b: *mut u32, edge_ani: *mut f32, n_edges: *mut u32) -> c_int;
+    pub fn psk_ctx_forest_stats(ctx: *mut PskCtx, edges: *mut u64, rounds: *mut u64, jump_passes: *mut u64) -> c_int;
     // the locality order of the references (slot_of: psk_db_size entries or null)
     pub fn psk_db_locality(db: *mut PskDb, slot_of: *mut u32, n_groups: *mut u32, is_identity: *mut u32) -> c_int;
     // the blocked seed index's layout as it stands (zeros before a query has built it), and the host-side bucket rule behind it
