@@ -45,7 +45,7 @@ void gsl_make_tab(const BatchQ* bq, size_t n_entries, const uint32_t* q_seeds, s
 }
 
 // LDS of one walk wave, the 16-byte units first: [EMIT: GSL_LW x p_cap staged 8-byte anchors][EMIT: lim1 per pair: p_cap x 8][EMIT: (cursor, first anchor) per pair, the step's lines]
-// [the walked block's pass row as eight (32 bits, prefix count) entries]
+// [the walked block's slot table: 256 x 2 bytes, local reference -> pair slot of the entry]
 // [COUNT: cursors: p_cap x 4; anchor-seed bitmaps, GSL_WORDS rows of p_cap + 1 words | EMIT: (cursor, first anchor) per pair: p_cap x 8; rows so far per pair: p_cap x 4]
 // anchors per staged line of the emit walk (GSL_LINE_N = 4: 32-byte lines, the smallest a write costs; 8: whole 64-byte lines - twice the LDS per wave). With 8-byte
 // anchors, 4 leaves a wave 13.9 instead of 22.1 KB at 256 pairs: eleven instead of seven waves per CU; measured on the 10 000 x 10 000 step, the emit walk alone
@@ -58,15 +58,14 @@ static_assert(GSL_LW == 8 || GSL_LW == 4 || GSL_LW == 2, "a staged line holds ei
 static size_t gsl_walk_lds(const GslArgs& A, bool emit) {
     const size_t nw = (A.n_refs + 63) / 64;
     (void)nw;
-    return (emit ? (8 * GSL_LW + 8 + 8) * (size_t)A.p_cap + 8 * 64 : 0) + 64 + 4 * (size_t)A.p_cap + (emit ? 0 : 4 * (size_t)GSL_WORDS * (A.p_cap + 1));
+    return (emit ? (8 * GSL_LW + 8 + 8) * (size_t)A.p_cap + 8 * 64 : 0) + 512 + 4 * (size_t)A.p_cap + (emit ? 0 : 4 * (size_t)GSL_WORDS * (A.p_cap + 1));
 }
 
 // (streaming - nontemporal - stores of the anchors were measured on the 10 000 x 10 000 step: the walk takes the same time and the DP kernel that reads the anchors next 178 instead of
 // 165 ms: plain stores; profiles/r5/r5_ablation.md)
 // TAGGED: a tagged index (psk_db::bsi_tagged) - the walk reads an entry's value alone and the match is "in the k-mer's bucket and tag == the k-mer's low byte"; otherwise key
 // and value, and the match is key == k-mer. The accessors below are all the loop knows of a value's top 16 bits (tag << 8 | local reference).
-__device__ __forceinline__ uint32_t gsl_ref_word(unsigned long long v) { return (uint32_t)(v >> 53) & 7u; }      // the local reference's group of 32
-__device__ __forceinline__ uint32_t gsl_ref_bit(unsigned long long v) { return (uint32_t)(v >> 48) & 31u; }      // ... and its bit within the group
+__device__ __forceinline__ uint32_t gsl_ref(unsigned long long v) { return (uint32_t)(v >> 48) & 0xFFu; }      // the local reference
 __device__ __forceinline__ uint32_t gsl_tag(unsigned long long v) { return (uint32_t)(v >> 56); }
 template <bool EMIT, bool TAGGED>
 __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
@@ -87,8 +86,8 @@ __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
     unsigned long long* s_lim = (unsigned long long*)(s_line + (EMIT ? GSL_LW * pc : 0u));     // EMIT: lim1 of the pair's open chunk
     uint2* s_cs = (uint2*)(s_lim + (EMIT ? pc : 0u));                                       // EMIT: (cursor, first anchor of the (pair, slice)): one 8-byte read
     uint2* s_fl = s_cs + (EMIT ? pc : 0u);                                                  // EMIT: the step's complete lines (pair | first slot << 16, first anchor of the line)
-    uint2* s_bp = s_fl + (EMIT ? 64u : 0u);                                                 // the block being walked: its 256 references of the query's pass row, 32 per entry: (bits, passing references before them)
-    uint32_t* s_cur = (uint32_t*)(s_bp + 8u);                                               // COUNT: anchors so far; EMIT: chunk-table rows of the pair so far
+    uint16_t* s_slot = (uint16_t*)(s_fl + (EMIT ? 64u : 0u));                               // the block being walked: local reference -> pair slot of the entry, 0xFFFF: not a pair of it (P <= 256: 16 bits)
+    uint32_t* s_cur = (uint32_t*)(s_slot + 256u);                                           // COUNT: anchors so far; EMIT: chunk-table rows of the pair so far
     uint32_t* s_rows = s_cur;
     uint32_t* s_bm = s_cur + pc;                                                            // COUNT: word w of pair j at [w * (pc + 1) + j]
     // The index comes in blocks of 2^BSI_BLOG references: only the blocks that hold a reference of one of the entry's pairs are walked (a run of the whole database's index
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
     if (EMIT && lane < (int)GSL_WORDS) unw = A.un[(size_t)(eb.y + te.y) * GSL_WORDS + lane];
     lds_wave_sync();
     // The walk (gsi_join_kernel's): a batch of 64 seeds has its k-mers loaded two batches ahead and its bucket bounds one batch ahead; its runs are cut into STEPS
-    // of 64 index entries, numbered through the batch, and the entries of step t + GSL_AHEAD are requested before step t is dealt out.
+    // of 64 index entries, taken seed after seed, and the entries of step t + GSL_AHEAD are requested before step t is dealt out.
     constexpr uint32_t GSL_AHEAD = 4;
     unsigned long long visited = 0;      // COUNT: index entries in the runs this lane's seeds found (psk_ctx_join_work)
     const uint32_t n_blk = A.blk_cnt[te.x];
@@ -117,13 +116,17 @@ __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
     const uint32_t blk = brow[8];
     const unsigned long long x_base = ((unsigned long long)brow[11] << 32) | brow[10];
     const uint32_t* __restrict__ x_key = A.g_key + x_base; const unsigned long long* __restrict__ x_val = A.g_val + x_base;      // (x_key: read by the untagged walk alone)
-    {   // the block's 256 references of the pass row -> eight (32 bits, passing references before them) entries: reference -> pair of the entry in ONE 8-byte LDS read
+    {   // the block's 256 references of the pass row -> the slot table, once per (wave, block): a step's entry -> pair of the entry is ONE 2-byte LDS read and a compare.
+        // A reference's slot is its rank among the query's passing references less rank_lo; one that does not pass, or ranks outside [rank_lo, rank_hi), has none
         lds_wave_sync();      // (the previous block's last lookups are through)
-        if (lane < 8) {
-            uint32_t run = brow[9];
+        uint32_t run = brow[9] - B.rank_lo;      // (scalar, like the eight words: the same for every lane)
 #pragma unroll
-            for (int u = 0; u < 7; u++) { const uint32_t w = brow[u]; if (u < lane) run += (uint32_t)__popc(w); }
-            s_bp[lane] = make_uint2(brow[lane], run);
+        for (uint32_t u = 0; u < 4; u++) {       // lane l: references l, 64 + l, 128 + l, 192 + l
+            const uint32_t w0 = brow[2 * u], w1 = brow[2 * u + 1];
+            const uint32_t rk = run + __builtin_amdgcn_mbcnt_hi(w1, __builtin_amdgcn_mbcnt_lo(w0, 0u));      // passing references before this one, from rank_lo on
+            const bool pass = (((unsigned long long)w1 << 32 | w0) >> lane) & 1ull;
+            s_slot[64u * u + (uint32_t)lane] = pass && rk < P ? (uint16_t)rk : (uint16_t)0xFFFFu;
+            run += (uint32_t)__popc(w0) + (uint32_t)__popc(w1);
         }
         lds_wave_sync();
     }
@@ -141,46 +144,56 @@ __global__ __launch_bounds__(64) void gsl_walk_kernel(GslArgs A) {
         if (EMIT && i < se) { qp = Q.pos[i]; qm = Q.meta[i]; }
         const uint32_t nst = (hi - lo + 63u) >> 6;
         if (!EMIT) visited += hi - lo;
-        uint32_t pre = nst;      // inclusive prefix sum over the lanes
+        // the batch's steps, seed after seed in lane order, each seed's in order: a SCALAR cursor (seed lane, next entry, end of the run) that pops the next seed with a
+        // run when its own is used up - two v_readlane per seed, nothing per step but scalar work. Past the batch's last step it yields h = 0: no lane is in range, and a
+        // step with h = 0 is the loop's end (a run is never empty: pending holds the seeds with hi > lo). The COUNT walk reads the seed's k-mer at the switch too; the
+        // EMIT walk reads k-mer, q pos and q meta per step as before: carrying them through the look-ahead costs it 17 to 21 spilled SGPRs
+        // The COUNT walk's gathers are UNCONDITIONAL: a lane past the run's end reads the step's first entry again (entry 0 of the block in a step past the batch's last:
+        // bsi_key / bsi_val are allocated 256 bytes beyond their last entry) and is excluded by the range test like a lane that holds no entry. Behind a branch on exec -
+        // what the compiler makes of a conditional gather - it cannot count the loads in flight and waits for ALL of them (vmcnt(0)) right behind the look-ahead's four
+        // requests: nothing was fetched ahead. Without the branch it waits for a group's entries at the end of the group before (count walk -6.4 ms per two steps of
+        // 10 000 x 10 000, the step -9 ms; the emit walk, measured the same way, gains nothing and keeps the conditional form; profiles/r10/r10_walk_skeleton.md)
+        constexpr bool KM_AT_SWITCH = !EMIT;
+        unsigned long long pending = __ballot(nst != 0);
+        uint32_t it_s = 0, it_x = 0, it_h = 0, it_k = 0;
+        uint32_t ns[GSL_AHEAD], nx[GSL_AHEAD], nh[GSL_AHEAD], nk[GSL_AHEAD], nkm[GSL_AHEAD]; unsigned long long nv[GSL_AHEAD];
+#define GSL_FETCH(u) do { \
+            if (it_x >= it_h) { \
+                if (pending) { \
+                    it_s = (uint32_t)__builtin_ctzll(pending); pending &= pending - 1ull; \
+                    it_x = (uint32_t)__builtin_amdgcn_readlane((int)lo, (int)it_s); it_h = (uint32_t)__builtin_amdgcn_readlane((int)hi, (int)it_s); \
+                    if (KM_AT_SWITCH) it_k = (uint32_t)__builtin_amdgcn_readlane((int)km, (int)it_s); \
+                } else { it_s = 0; it_x = 0; it_h = 0; } \
+            } \
+            ns[u] = it_s; nx[u] = it_x; nh[u] = it_h; nkm[u] = it_k; nk[u] = 0xFFFFFFFFu; nv[u] = 0ull; \
+            if (EMIT) { if (nx[u] + (uint32_t)lane < nh[u]) { if (!TAGGED) nk[u] = x_key[nx[u] + lane]; nv[u] = x_val[nx[u] + lane]; } } \
+            else { const uint32_t ix = nx[u] + (uint32_t)lane < nh[u] ? nx[u] + (uint32_t)lane : nx[u]; if (!TAGGED) nk[u] = x_key[ix]; nv[u] = x_val[ix]; } \
+            it_x += 64u; \
+            } while (0)
 #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(pre, o); if (lane >= o) pre += y; }
-        const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)pre, 63);
-        pre -= nst;
-        uint32_t ns[GSL_AHEAD], nx[GSL_AHEAD], nh[GSL_AHEAD], nk[GSL_AHEAD]; unsigned long long nv[GSL_AHEAD];
-#define GSL_FETCH(t, u) do { \
-            ns[u] = 0; nx[u] = 0; nh[u] = 0; nk[u] = 0xFFFFFFFFu; nv[u] = 0ull; \
-            if ((t) < T) { \
-                const unsigned long long own = __ballot(nst != 0 && pre <= (t)); \
-                ns[u] = 63u - (uint32_t)__clzll((long long)own); \
-                nx[u] = (uint32_t)__builtin_amdgcn_readlane((int)lo, (int)ns[u]) + 64u * ((t) - (uint32_t)__builtin_amdgcn_readlane((int)pre, (int)ns[u])); \
-                nh[u] = (uint32_t)__builtin_amdgcn_readlane((int)hi, (int)ns[u]); \
-                if (nx[u] + (uint32_t)lane < nh[u]) { if (!TAGGED) nk[u] = x_key[nx[u] + lane]; nv[u] = x_val[nx[u] + lane]; } \
-            } } while (0)
+        for (uint32_t u = 0; u < GSL_AHEAD; u++) GSL_FETCH(u);
+        for (;;) {
+            uint32_t cs[GSL_AHEAD], cx[GSL_AHEAD], ch[GSL_AHEAD], ck[GSL_AHEAD], ckm[GSL_AHEAD]; unsigned long long cv[GSL_AHEAD];
 #pragma unroll
-        for (uint32_t u = 0; u < GSL_AHEAD; u++) GSL_FETCH(u, u);
-        for (uint32_t t0 = 0; t0 < T; t0 += GSL_AHEAD) {
-            uint32_t cs[GSL_AHEAD], cx[GSL_AHEAD], ch[GSL_AHEAD], ck[GSL_AHEAD]; unsigned long long cv[GSL_AHEAD];
+            for (uint32_t u = 0; u < GSL_AHEAD; u++) { cs[u] = ns[u]; cx[u] = nx[u]; ch[u] = nh[u]; ck[u] = nk[u]; cv[u] = nv[u]; ckm[u] = nkm[u]; }
+            if (ch[0] == 0) break;      // the batch's steps are dealt out
 #pragma unroll
-            for (uint32_t u = 0; u < GSL_AHEAD; u++) { cs[u] = ns[u]; cx[u] = nx[u]; ch[u] = nh[u]; ck[u] = nk[u]; cv[u] = nv[u]; }
-#pragma unroll
-            for (uint32_t u = 0; u < GSL_AHEAD; u++) GSL_FETCH(t0 + GSL_AHEAD + u, u);
+            for (uint32_t u = 0; u < GSL_AHEAD; u++) GSL_FETCH(u);
             // the pairs of the group's entries first, all four steps' LDS reads in flight together (they depend on nothing but the entries), then the steps one by one:
             // what is sequential - a pair's cursor - is only in the second part
-            uint32_t slots[GSL_AHEAD]; uint2 bps[GSL_AHEAD];
+            uint32_t slots[GSL_AHEAD], sl[GSL_AHEAD];
 #pragma unroll
-            for (uint32_t u = 0; u < GSL_AHEAD; u++) bps[u] = s_bp[gsl_ref_word(cv[u])];      // (every lane reads: a lane without an entry has v = 0 - the block's first word; an entry's reference is of this block)
+            for (uint32_t u = 0; u < GSL_AHEAD; u++) sl[u] = s_slot[gsl_ref(cv[u])];      // (every lane reads: a lane without an entry has v = 0 - the block's first reference -, in the COUNT walk some entry of the block; an entry's reference is of this block)
 #pragma unroll
             for (uint32_t u = 0; u < GSL_AHEAD; u++) {
-                const uint32_t skm = (uint32_t)__builtin_amdgcn_readlane((int)km, (int)cs[u]);
-                const uint32_t b = gsl_ref_bit(cv[u]), rk = bps[u].y + (uint32_t)__popc(bps[u].x & ~(~0u << b)) - B.rank_lo;
+                const uint32_t skm = KM_AT_SWITCH ? ckm[u] : (uint32_t)__builtin_amdgcn_readlane((int)km, (int)cs[u]);
                 // (a tagged index: the bucket holds the k-mers that agree with the seed's above bit g_shift <= 8, the tag tells the rest. Steps past the batch's last: nh = 0, no lane is in range; nk = 0xFFFFFFFF is no k-mer)
                 const bool hit = TAGGED ? gsl_tag(cv[u]) == (skm & 0xFFu) : ck[u] == skm;
-                const bool ok = cx[u] + (uint32_t)lane < ch[u] && hit && ((bps[u].x >> b) & 1u) && rk < P;
-                slots[u] = ok ? rk : 0xFFFFFFFFu;
+                slots[u] = cx[u] + (uint32_t)lane < ch[u] && hit && sl[u] != 0xFFFFu ? sl[u] : 0xFFFFFFFFu;
             }
 #pragma unroll
             for (uint32_t u = 0; u < GSL_AHEAD; u++) {
-                if (t0 + u >= T) break;
+                if (ch[u] == 0) break;
                 const uint32_t s = cs[u]; const unsigned long long v = cv[u];
                 const uint32_t slot = slots[u];
                 const bool valid = slot != 0xFFFFFFFFu;
