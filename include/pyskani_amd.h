@@ -96,6 +96,20 @@ typedef struct {
     uint32_t query;     /* index of the query within the call (sharded runs: the global index); bit 31: the regression model produced `ani` */
 } psk_hit_min;
 
+/* psk_hit_min and the bootstrap interval of `ani` (psk_query_many_ci), 28 bytes; `query` as in psk_hit_min */
+typedef struct {
+    float ani, af_query, af_ref;
+    uint32_t ref_index;
+    uint32_t query;
+    float ci_lo, ci_hi; /* the 5 % and 95 % points of the resample means, around `ani` */
+} psk_hit_ci;
+/* Options of the interval calls; a NULL pointer means {0, 0, 0}. */
+typedef struct {
+    uint32_t iterations; /* resamples B: 0 = 100, else 20 <= B <= 1024 */
+    uint32_t reserved;   /* must be 0 */
+    uint64_t seed;       /* of the draw stream */
+} psk_ci_opts;
+
 typedef struct { uint32_t kmer, pos, contig, canon; } psk_seed; /* export record (parity tests) */
 
 const char* psk_last_error(void);
@@ -103,7 +117,7 @@ const char* psk_version(void);
 /* The C-ABI's revision: raised whenever an entry point's parameters or a structure's layout change (4: psk_sketch_unpack takes the extent of its source buffer as third
  * argument; 5: psk_hit_min / psk_query_many_min / psk_gather_hits_min / psk_ctx_join_work added;
  * 6: psk_db_locality added; 7: psk_ctx_rerun_stats added). psk_query_many_tri and psk_query_many_tri_min came after 7 WITHOUT raising it: no existing argument
- * list or structure moved, and a binding that wants them detects them by their presence (dlsym); psk_cluster_records, psk_ctx_cluster_stats, psk_ctx_tier_stats, psk_cluster_forest and psk_ctx_forest_stats likewise. A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
+ * list or structure moved, and a binding that wants them detects them by their presence (dlsym); psk_cluster_records, psk_ctx_cluster_stats, psk_ctx_tier_stats, psk_cluster_forest, psk_ctx_forest_stats and the interval calls (psk_chain_ci, psk_query_many_ci, psk_ctx_interval_stats, psk_ci_draw, psk_ci_ranks) likewise. A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
  * written against before it calls anything else: an argument list that moved is a memory error, not a link error. */
 #define PSK_ABI_VERSION 7
 int psk_abi_version(void);
@@ -116,7 +130,7 @@ void psk_ctx_destroy(psk_ctx* ctx);
 psk_status psk_ctx_synchronize(psk_ctx* ctx);
 /* Measurement: bracket the named kernels' launches with HIP events on the ctx stream.
  * kernel in {"sketch_scan","sketch_emit","sketch_sort","screen","anchor","chain_chunk",
- * "select","pair_reduce","anchor_emit"}; "reset" clears the accumulators. psk_ctx_timing synchronises the stream. */
+ * "select","pair_reduce","anchor_emit","interval"}; "reset" clears the accumulators. psk_ctx_timing synchronises the stream. */
 psk_status psk_ctx_set_timing(psk_ctx* ctx, int on);
 /* Shader clock the device holds under an integer-VALU load: a fixed ~1 ms micro-kernel (v_alignbit_b32 chains, 4 cycles per
  * wave64 instruction on gfx950) timed with HIP events; *mhz = cycles / duration, *ms = the duration (may be NULL). */
@@ -396,6 +410,36 @@ psk_status psk_cluster_forest(psk_ctx* ctx, const psk_hit_min* recs, uint64_t n_
 /* Measurement: the context's last psk_cluster_forest call that reached the device - undirected edges of its graph, Boruvka rounds that hooked at least one component,
  * pointer-jump launches (those that found something left to do; the launches behind them return at once). Any pointer may be NULL. */
 psk_status psk_ctx_forest_stats(psk_ctx* ctx, uint64_t* edges, uint64_t* rounds, uint64_t* jump_passes);
+
+/* ---- confidence intervals of the ANI: skani's --ci, a 5 % - 95 % bootstrap interval resampled from the per-chunk estimates whose mean the ANI is (csrc/interval.hip).
+ * The rule is a function of the pair's chunk values, the options and nothing else - not of the batch, lane, round or slot the pair was computed in.
+ * Values
+ *  - v[0..m) are the values of the chunks that kept a chain, in chunk order, as doubles: pow(min(1, anchors / max(1, seeds - 1)), 1 / k), the reduce stage's own expression.
+ * Resampling, for resample b in [0, B) and draw j in [0, m)
+ *  - h = mm_hash64(seed + ((uint64)b << 32) + (j >> 1)), a wrap-around 64-bit sum; w = the high word of h for an odd j, the low word for an even one.
+ *  - idx = (uint32)(((uint64)w * m) >> 32), and mean_b = (v[idx_0] + v[idx_1] + ... + v[idx_(m-1)]) / m in double, added in draw order.
+ * Bounds
+ *  - With s the B means in ascending order: ci_lo = (float)s[B / 20], ci_hi = (float)s[B - 1 - B / 20] - s[5] and s[94] for B = 100.
+ *  - A pair whose ani_raw is negative (no chunk kept a chain, or below min_aligned_frac): ci_lo = ci_hi = -1.
+ *  - Where the regression model produced `ani` (learned == 1), both bounds are moved by ani - ani_raw in float and clamped to [0, 1]: the interval sits around the
+ *    number the caller sees. m == 1 gives ci_lo == ci_hi == ani_raw.
+ * Refusals, before any device work, PSK_EINVAL: a NULL argument (the options may be NULL), iterations outside {0} and [20, 1024], reserved != 0, and median or robust
+ * set in the query options - the interval is defined for the mean estimator. The context stays usable.
+ * A call that does not ask for intervals launches nothing of this and returns what it returned before. */
+/* psk_chain and the bounds of every pair: out[] is bit-equal to psk_chain's, ci_lo[] / ci_hi[] have n_refs entries. */
+psk_status psk_chain_ci(psk_ctx* ctx, const psk_sketch* const* refs, uint32_t n_refs, const psk_sketch* query, const psk_query_opts* o, const psk_ci_opts* ci,
+                        psk_hit* out, float* ci_lo, float* ci_hi);
+/* psk_query_many_min (query_key == NULL) or psk_query_many_tri_min (query_key given) with psk_hit_ci records: same hits, same order, the five shared fields bit-equal. */
+psk_status psk_query_many_ci(psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const int64_t* query_key, uint64_t ref_base,
+                             const psk_query_opts* opts, const psk_ci_opts* ci, psk_hit_ci** hits, uint64_t* offsets);
+/* Measurement, since the last reset: pairs that received bounds and draws made for them (summed over the completed batches), and launches of the three size tiers -
+ * tier_launches[0] one wave per pair (chunk tables of up to 512 rows), [1] one workgroup per pair (up to 4096 kept values), [2] values in global memory (beyond).
+ * Any pointer may be NULL. */
+psk_status psk_ctx_interval_stats(psk_ctx* ctx, uint64_t* pairs, uint64_t* draws, uint64_t* tier_launches /* 3 entries */, int reset);
+/* Host only, exposed for tests: the draw and the ranks of the rule above, from the inline functions the kernels use. psk_ci_draw: idx of draw j of resample b among m
+ * values (m == 0: 0). psk_ci_ranks: *n = the resamples `iterations` stands for (0 -> 100), *lo_rank = n / 20, *hi_rank = n - 1 - n / 20; NULL pointers are skipped. */
+uint32_t psk_ci_draw(uint64_t seed, uint32_t b, uint32_t j, uint32_t m);
+void psk_ci_ranks(uint32_t iterations, uint32_t* n, uint32_t* lo_rank, uint32_t* hi_rank);
 
 #ifdef __cplusplus
 }

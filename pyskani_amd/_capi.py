@@ -37,6 +37,17 @@ class HitMin(C.Structure):
     _fields_ = [("ani", C.c_float), ("af_query", C.c_float), ("af_ref", C.c_float), ("ref_index", C.c_uint32), ("query", C.c_uint32)]
 
 
+class HitCi(C.Structure):
+    """psk_hit_ci: psk_hit_min and the bootstrap interval of `ani`, 28 bytes"""
+    _fields_ = [("ani", C.c_float), ("af_query", C.c_float), ("af_ref", C.c_float), ("ref_index", C.c_uint32), ("query", C.c_uint32),
+                ("ci_lo", C.c_float), ("ci_hi", C.c_float)]
+
+
+class CiOpts(C.Structure):
+    """psk_ci_opts: iterations (0: 100, else 20 .. 1024), reserved (0), seed of the draw stream"""
+    _fields_ = [("iterations", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
+
+
 class ClusterOpts(C.Structure):
     """psk_cluster_opts: min_ani (<= 0: 0.95), min_af (< 0: 0.5; 0: no aligned-fraction condition), af_rule (0 both, 1 either), linkage (0 greedy, 1 single)"""
     _fields_ = [("min_ani", C.c_double), ("min_af", C.c_double), ("af_rule", C.c_int32), ("linkage", C.c_int32)]
@@ -63,6 +74,7 @@ SYMBOLS = [
     "psk_sketch_host", "psk_sketch_many_host", "psk_sketch_batch_device", "psk_sketch_free", "psk_sketch_free_many", "psk_sketch_info",
     "psk_sketch_export", "psk_sketch_contig_lens", "psk_sketch_import", "psk_db_create", "psk_db_destroy", "psk_db_add", "psk_db_size",
     "psk_db_name", "psk_db_sketch", "psk_db_locality", "psk_db_seed_index_info", "psk_bsi_plan", "psk_screen", "psk_chain", "psk_query", "psk_query_host", "psk_query_many", "psk_query_many_min", "psk_query_many_tri", "psk_query_many_tri_min", "psk_cluster_records", "psk_ctx_cluster_stats", "psk_cluster_forest", "psk_ctx_forest_stats", "psk_gather_hits_min",
+    "psk_chain_ci", "psk_query_many_ci", "psk_ctx_interval_stats", "psk_ci_draw", "psk_ci_ranks",
     "psk_sketch_pack_size", "psk_sketch_pack", "psk_sketch_unpack", "psk_sketch_pack_many", "psk_ctx_clock_probe", "psk_ctx_work", "psk_ctx_join_work",
     "psk_comm_unique_id", "psk_comm_create", "psk_comm_destroy", "psk_comm_info", "psk_gather_hits", "psk_gather_sketches",
     "psk_model_create", "psk_model_load_json", "psk_model_load_file", "psk_model_free", "psk_model_info", "psk_model_predict",
@@ -142,6 +154,14 @@ def load():
     lib.psk_ctx_cluster_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     lib.psk_cluster_forest.argtypes = [vp, vp, u64, u32, C.POINTER(ClusterOpts), vp, vp, vp, C.POINTER(u32)]
     lib.psk_ctx_forest_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    if hasattr(lib, "psk_query_many_ci"):      # (came after ABI 7 without raising it: detected by its presence)
+        lib.psk_chain_ci.argtypes = [vp, C.POINTER(vp), u32, vp, C.POINTER(QueryOpts), C.POINTER(CiOpts), C.POINTER(Hit), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        lib.psk_query_many_ci.argtypes = [vp, C.POINTER(vp), u32, C.POINTER(C.c_int64), u64, C.POINTER(QueryOpts), C.POINTER(CiOpts), C.POINTER(C.POINTER(HitCi)), C.POINTER(u64)]
+        lib.psk_ctx_interval_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.c_int]
+        lib.psk_ci_draw.argtypes = [u64, u32, u32, u32]
+        lib.psk_ci_draw.restype = u32
+        lib.psk_ci_ranks.argtypes = [u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+        lib.psk_ci_ranks.restype = None
     lib.psk_gather_hits_min.argtypes = [vp, vp, u64, C.POINTER(C.POINTER(HitMin)), C.POINTER(u64), C.POINTER(u64)]
     lib.psk_sketch_pack_size.argtypes = [vp, C.POINTER(u64)]
     lib.psk_sketch_pack.argtypes = [vp, vp, u64]

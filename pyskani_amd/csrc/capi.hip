@@ -254,6 +254,22 @@ psk_status psk_ctx_tier_stats(psk_ctx* c, uint64_t* out, int n, int reset) {
     if (reset) for (int i = 0; i < TIER_COUNT; i++) c->tier[i] = 0;
     return PSK_OK;
 }
+psk_status psk_ctx_interval_stats(psk_ctx* c, uint64_t* pairs, uint64_t* draws, uint64_t* tier_launches, int reset) {
+    if (!c) { psk_set_error("NULL ctx"); return PSK_EINVAL; }
+    if (pairs) *pairs = c->ci_pairs.load();
+    if (draws) *draws = c->ci_draws.load();
+    if (tier_launches) for (int i = 0; i < 3; i++) tier_launches[i] = c->ci_tier[i].load();
+    if (reset) { c->ci_pairs = 0; c->ci_draws = 0; for (int i = 0; i < 3; i++) c->ci_tier[i] = 0; }
+    return PSK_OK;
+}
+uint32_t psk_ci_draw(uint64_t seed, uint32_t b, uint32_t j, uint32_t m) { return m ? ci_draw(seed, b, j, m) : 0u; }
+void psk_ci_ranks(uint32_t iterations, uint32_t* n, uint32_t* lo_rank, uint32_t* hi_rank) {
+    uint32_t B, lo, hi;
+    ci_ranks(iterations, &B, &lo, &hi);
+    if (n) *n = B;
+    if (lo_rank) *lo_rank = lo;
+    if (hi_rank) *hi_rank = hi;
+}
 psk_status psk_device_alloc(psk_ctx* c, size_t bytes, void** dptr) {
     if (!c || !dptr) { psk_set_error("device_alloc: NULL argument"); return PSK_EINVAL; }
     PSK_HIP(hipSetDevice(c->device));
@@ -511,6 +527,23 @@ psk_status psk_chain(psk_ctx* ctx, const psk_sketch* const* refs, uint32_t n_ref
     return chain_impl(lg.lane, refs, n_refs, q, o, out);
 }
 
+// the interval calls' options, checked before any device work; *out = the options with the NULL default filled in
+static psk_status ci_args(const psk_query_opts* o, const psk_ci_opts* ci, psk_ci_opts* out, const char* who) {
+    *out = ci ? *ci : psk_ci_opts{0, 0, 0};
+    if (out->iterations != 0 && (out->iterations < CI_MIN_ITER || out->iterations > CI_MAX_ITER)) { psk_set_error("%s: iterations must be 0 (= %u) or within %u .. %u, not %u", who, CI_DEFAULT_ITER, CI_MIN_ITER, CI_MAX_ITER, out->iterations); return PSK_EINVAL; }
+    if (out->reserved != 0) { psk_set_error("%s: psk_ci_opts.reserved must be 0", who); return PSK_EINVAL; }
+    if (o->median || o->robust) { psk_set_error("%s: the interval is defined for the mean estimator; it cannot be combined with median or robust", who); return PSK_EINVAL; }
+    return PSK_OK;
+}
+psk_status psk_chain_ci(psk_ctx* ctx, const psk_sketch* const* refs, uint32_t n_refs, const psk_sketch* q, const psk_query_opts* o, const psk_ci_opts* ci,
+                        psk_hit* out, float* ci_lo, float* ci_hi) {
+    if (!ctx || !q || !o || (n_refs && (!refs || !out || !ci_lo || !ci_hi))) { psk_set_error("chain_ci: NULL argument"); return PSK_EINVAL; }
+    psk_ci_opts c;
+    PSK_TRY(ci_args(o, ci, &c, "chain_ci"));
+    PSK_LANE(lg, ctx);
+    return chain_impl(lg.lane, refs, n_refs, q, o, out, &c, ci_lo, ci_hi);
+}
+
 static psk_status hits_out(HitList& all, psk_hit** hits) {
     if (!all.p) { all.p = (psk_hit*)malloc(sizeof(psk_hit)); if (!all.p) { psk_set_error("out of host memory"); return PSK_ENOMEM; } }      // no hit: still a pointer psk_free takes
     *hits = all.release();      // the list's own malloc'd array: no copy
@@ -614,6 +647,22 @@ psk_status psk_query_many_tri_min(psk_db* db, const psk_sketch* const* queries, 
     HitListMin all;
     PSK_TRY(query_many_min_impl(lg.lane, db, queries, n_queries, o, all, offsets, n_queries ? query_key : nullptr, ref_base));
     if (!all.p) { all.p = (psk_hit_min*)malloc(sizeof(psk_hit_min)); if (!all.p) { psk_set_error("out of host memory"); return PSK_ENOMEM; } }      // no hit: still a pointer psk_free takes
+    *hits = all.release();
+    return PSK_OK;
+}
+
+psk_status psk_query_many_ci(psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const int64_t* query_key, uint64_t ref_base,
+                             const psk_query_opts* o, const psk_ci_opts* ci, psk_hit_ci** hits, uint64_t* offsets) {
+    if (!db || (!queries && n_queries) || !o || !hits || !offsets) { psk_set_error("query_many_ci: NULL argument"); return PSK_EINVAL; }
+    if (query_key) PSK_TRY(tri_args(db, queries, n_queries, query_key, ref_base, o, hits, offsets, "query_many_ci"));
+    psk_ci_opts c;
+    PSK_TRY(ci_args(o, ci, &c, "query_many_ci"));
+    *hits = nullptr;
+    offsets[0] = 0;
+    PSK_LANE(lg, db->ctx);
+    HitListCi all;
+    PSK_TRY(query_many_ci_impl(lg.lane, db, queries, n_queries, o, &c, all, offsets, n_queries ? query_key : nullptr, ref_base));
+    if (!all.p) { all.p = (psk_hit_ci*)malloc(sizeof(psk_hit_ci)); if (!all.p) { psk_set_error("out of host memory"); return PSK_ENOMEM; } }      // no hit: still a pointer psk_free takes
     *hits = all.release();
     return PSK_OK;
 }

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void work_rows_kernel(const ChunkOut* __restri
     }
 }
 
-psk_status chain_layout(Lane* ctx, size_t n_pairs, size_t n_items, size_t n_rows, size_t n_bq, ChainBufs* L) {
+psk_status chain_layout(Lane* ctx, size_t n_pairs, size_t n_items, size_t n_rows, size_t n_bq, ChainBufs* L, bool want_ci) {
     const size_t gi = (n_items + 255) / 256, gi_sum = std::max(gi, (n_pairs + 3) / 4);
     size_t o_pairs = 0, o_sbase = al256(o_pairs + sizeof(PairDesc) * n_pairs), o_cbase = al256(o_sbase + 4 * (n_pairs + 1)),
            o_pstart = al256(o_cbase + 4 * (n_pairs + 1)), o_lb = al256(o_pstart + 4 * (n_pairs + 1)),
@@ -169,8 +169,10 @@ psk_status chain_layout(Lane* ctx, size_t n_pairs, size_t n_items, size_t n_rows
            o_qr = al256(o_bsum + 8 * (gi_sum + 1)), o_bq = al256(o_qr + 8 * n_pairs), o_bp = al256(o_bq + sizeof(BatchQ) * (n_bq + 1)),
            o_rp = al256(o_bp + 4 * (gi + 1)), o_live = al256(o_rp + 4 * (n_rows + 1)), o_big = al256(o_live + 4 * (n_pairs + 1)),
            o_huge = al256(o_big + 4 * (n_pairs + 1)), o_end = o_huge + 4 * (n_pairs + 1);
-    PSK_TRY(ctx->q_b.reserve(o_end));
+    const size_t o_ci = al256(o_end);      // (behind everything else: nothing moves when it is there)
+    PSK_TRY(ctx->q_b.reserve(want_ci ? o_ci + sizeof(float2) * n_pairs : o_end));
     char* B = (char*)ctx->q_b.p;
+    L->ci = want_ci ? (float2*)(B + o_ci) : nullptr;
     L->pairs = (PairDesc*)(B + o_pairs); L->sbase = (uint32_t*)(B + o_sbase); L->cbase = (uint32_t*)(B + o_cbase); L->pstart = (uint32_t*)(B + o_pstart);
     L->lbcnt = (uint2*)(B + o_lb); L->aoff = (uint32_t*)(B + o_aoff); L->nch = (uint32_t*)(B + o_nch); L->chunks = (uint2*)(B + o_chunks); L->row_q0 = (uint2*)(B + o_rq0);
     L->cout = (ChunkOut*)(B + o_cout); L->hits = (psk_hit*)(B + o_hits); L->hits_sel = (psk_hit*)(B + o_sel); L->misc = (uint32_t*)(B + o_misc);
@@ -185,7 +187,7 @@ psk_status chain_layout(Lane* ctx, size_t n_pairs, size_t n_items, size_t n_rows
 // Anchor arrays are sized optimistically (cap anchors); the 64-bit anchor total travels back with the hits and the caller
 // reruns the batch with a larger capacity if it did not fit (emit and every later kernel stay inside cap).
 psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_items, size_t n_rows, const psk_params& prm,
-                     const psk_query_opts* o, const SketchDesc* d_qd, const SketchDesc* d_rd, uint64_t cap, bool wide, const Switches& sw, bool probe_ok) {
+                     const psk_query_opts* o, const SketchDesc* d_qd, const SketchDesc* d_rd, uint64_t cap, bool wide, const Switches& sw, bool probe_ok, const psk_ci_opts* ci) {
     hipStream_t st = ctx->stream;
     const int force_serial = sw.chain_serial.get() != nullptr;
     // misc[0..15] status / counts, misc[11] pairs for select_huge_kernel, misc[16..17] the 64-bit anchor total, misc[32..47] the group barriers: zeroed by pair_table_kernel
@@ -562,6 +564,22 @@ psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_i
     // learned-ANI regression (lib.rs:611-614): explicit request, or the default rule c >= 70 && !median when a model is given
     const bool learned = o->model && (o->learned_ani == 1 || (o->learned_ani == -1 && prm.c >= 70 && !o->median));
     if (learned) learned_apply_launch(o->model, L.hits, L.pair_qr, d_qd, d_rd, n_pairs, st);
+    if (ci) {      // bootstrap intervals (interval.hip): behind the regression, whose record says whether the bounds move with the ANI
+        if (!L.ci) { psk_set_error("internal: intervals asked for without their array"); return PSK_EHIP; }
+        IntervalArgs IA{};
+        IA.chunks = L.cout; IA.n_chunks = L.nch; IA.cbase = L.cbase; IA.live = R.live; IA.n_live = R.n_live; IA.hits = L.hits; IA.out = L.ci;
+        IA.work = (unsigned long long*)(L.misc + 24);      // (zeroed by pair_table_kernel with the other status words)
+        IA.k = prm.k; IA.seed = ci->seed;
+        ci_ranks(ci->iterations, &IA.B, &IA.lo_rank, &IA.hi_rank);
+        IA.b_pad = (IA.B + 63u) & ~63u;
+        if (L.rows_pair_max > (uint32_t)RED_CAP) {      // some pair may keep more values than LDS holds
+            PSK_TRY(ctx->q_f.reserve(sizeof(double) * (n_rows + 256)));
+            IA.big_vals = (double*)ctx->q_f.p;
+        }
+        ctx->t_begin(K_INTERVAL);
+        interval_launch(IA, n_pairs, L.rows_pair_max, use_live, ctx->dev->ci_tier, st);
+        ctx->t_end();
+    }
     return PSK_OK;
 }
 
@@ -601,7 +619,8 @@ psk_status chain_check(const ChainTail& T, uint32_t n_pairs, uint64_t* cap, bool
 
 
 // one launch sequence over an explicit list of (ref, query) pairs; out[p] in pair order
-psk_status chain_batch(Lane* ctx, const HostPair* hp, uint32_t n_pairs, const psk_query_opts* o, psk_hit* out, const Switches& sw) {
+psk_status chain_batch(Lane* ctx, const HostPair* hp, uint32_t n_pairs, const psk_query_opts* o, psk_hit* out, const Switches& sw,
+                       const psk_ci_opts* ci, float* ci_lo, float* ci_hi) {
     hipStream_t st = ctx->stream;
     // descriptor table: one entry per distinct sketch
     std::unordered_map<const psk_sketch*, uint32_t> slot;
@@ -618,12 +637,12 @@ psk_status chain_batch(Lane* ctx, const HostPair* hp, uint32_t n_pairs, const ps
     }
     h_sbase[n_pairs] = (uint32_t)items; h_cbase[n_pairs] = (uint32_t)rows;
     if (items == 0 || rows == 0) {
-        for (uint32_t p = 0; p < n_pairs; p++) { out[p] = psk_hit{}; out[p].ani = -1.0f; out[p].ani_raw = -1.0f; }
+        for (uint32_t p = 0; p < n_pairs; p++) { out[p] = psk_hit{}; out[p].ani = -1.0f; out[p].ani_raw = -1.0f; if (ci) { ci_lo[p] = -1.0f; ci_hi[p] = -1.0f; } }
         return PSK_OK;
     }
     if (items >= 0xFFFFFF00ull || rows >= 0xFFFFFF00ull) { psk_set_error("batch of %u pairs exceeds the per-launch limits", n_pairs); return PSK_ELIMIT; }
     ChainBufs L;
-    PSK_TRY(chain_layout(ctx, n_pairs, (size_t)items, (size_t)rows, 0, &L));
+    PSK_TRY(chain_layout(ctx, n_pairs, (size_t)items, (size_t)rows, 0, &L, ci != nullptr));
     PSK_TRY(ctx->q_h.reserve(al256(sizeof(SketchDesc) * descs.size()) + 256));
     SketchDesc* d_desc = (SketchDesc*)ctx->q_h.p;
     PSK_HIP(hipMemcpyAsync(d_desc, descs.data(), sizeof(SketchDesc) * descs.size(), hipMemcpyHostToDevice, st));
@@ -632,28 +651,32 @@ psk_status chain_batch(Lane* ctx, const HostPair* hp, uint32_t n_pairs, const ps
     PSK_HIP(hipMemcpyAsync(L.cbase, h_cbase.data(), 4 * (size_t)(n_pairs + 1), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(pair_build_list_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, L.pair_qr, d_desc, d_desc, n_pairs, L.pairs);
     void* hpin;
-    PSK_TRY(ctx->pinned(sizeof(psk_hit) * n_pairs + 512, &hpin));
+    const size_t o_hci = al256(sizeof(psk_hit) * n_pairs + 512);      // (the bounds' staging, behind the hits)
+    PSK_TRY(ctx->pinned(ci ? o_hci + sizeof(float2) * n_pairs : sizeof(psk_hit) * n_pairs + 512, &hpin));
     ChainTail* T = (ChainTail*)hpin; psk_hit* h_hits = (psk_hit*)((char*)hpin + 256);
+    const float2* h_ci = (const float2*)((char*)hpin + o_hci);
     uint64_t cap = anchor_cap_for(ctx, (size_t)items);
     bool wide = sw.join_wide();
     for (int attempt = 0;; attempt++) {
-        PSK_TRY(chain_run(ctx, L, n_pairs, (size_t)items, (size_t)rows, hp[0].q->params, o, d_desc, d_desc, cap, wide, sw));
-        PSK_HIP(hipMemcpyAsync(T, L.misc, 256 + sizeof(psk_hit) * n_pairs, hipMemcpyDeviceToHost, st));      // status words, anchor total and the hits behind them: one copy (ChainTail mirrors misc[0..17])
+        PSK_TRY(chain_run(ctx, L, n_pairs, (size_t)items, (size_t)rows, hp[0].q->params, o, d_desc, d_desc, cap, wide, sw, false, ci));
+        PSK_HIP(hipMemcpyAsync(T, L.misc, 256 + sizeof(psk_hit) * n_pairs, hipMemcpyDeviceToHost, st));
+        if (ci) PSK_HIP(hipMemcpyAsync((void*)h_ci, L.ci, sizeof(float2) * n_pairs, hipMemcpyDeviceToHost, st));      // status words, anchor total and the hits behind them: one copy (ChainTail mirrors misc[0..17])
         PSK_HIP(hipStreamSynchronize(st));      // the ONE synchronisation of a launch sequence (also keeps the host staging above alive)
         ctx->huge_release();
         bool retry; const bool was_wide = wide;
         PSK_TRY(chain_check(*T, n_pairs, &cap, &wide, &retry));
         count_rerun(ctx->dev, was_wide, wide, retry);
-        if (!retry) { ctx->dev->w_pairs += n_pairs; ctx->dev->w_items += items; ctx->dev->w_anchors += T->total64; ctx->dev->w_cands += T->cands; ctx->dev->w_rows += T->rows; count_tier_pairs(ctx->dev, T->misc); break; }
+        if (!retry) { ctx->dev->w_pairs += n_pairs; ctx->dev->w_items += items; ctx->dev->w_anchors += T->total64; ctx->dev->w_cands += T->cands; ctx->dev->w_rows += T->rows; count_tier_pairs(ctx->dev, T->misc); if (ci) count_interval(ctx->dev, T); break; }
         if (attempt >= 3) { psk_set_error("internal: anchor capacity did not converge"); return PSK_EHIP; }
     }
     for (uint32_t p = 0; p < n_pairs; p++) { out[p] = h_hits[p]; out[p].reserved = 0; }
+    if (ci) for (uint32_t p = 0; p < n_pairs; p++) { ci_lo[p] = h_ci[p].x; ci_hi[p] = h_ci[p].y; }
     return PSK_OK;
 }
 
 // chain an arbitrary list of (ref, query) pairs; out[i] belongs to pair i (ref_index is left to the caller)
 psk_status chain_pairs_impl(Lane* ctx, const psk_sketch* const* refs, const psk_sketch* const* queries, uint32_t n,
-                            const psk_query_opts* o, psk_hit* out) {
+                            const psk_query_opts* o, psk_hit* out, const psk_ci_opts* ci, float* ci_lo, float* ci_hi) {
     if (!ctx || !o || (n && (!refs || !queries || !out))) { psk_set_error("chain: NULL argument"); return PSK_EINVAL; }
     const Switches sw = Switches::read();      // ($PSK_*: once per call)
     if (o->learned_ani == 1 && !o->model) { psk_set_error("learned ANI requested but no regression model is loaded (skani's GBDT weights are embedded in the skani crate; supply them with psk_model_load_file)"); return PSK_ENOMODEL; }
@@ -677,13 +700,13 @@ psk_status chain_pairs_impl(Lane* ctx, const psk_sketch* const* refs, const psk_
         hp.clear();
         uint64_t items = 0; uint32_t e = b;
         while (e < n && hp.size() < MAX_PAIRS && (hp.empty() || items + queries[e]->n_seeds <= MAX_ITEMS)) { hp.push_back({refs[e], queries[e]}); items += queries[e]->n_seeds; e++; }
-        psk_status rc = chain_batch(ctx, hp.data(), (uint32_t)hp.size(), o, out + b, sw);
+        psk_status rc = chain_batch(ctx, hp.data(), (uint32_t)hp.size(), o, out + b, sw, ci, ci ? ci_lo + b : nullptr, ci ? ci_hi + b : nullptr);
         if (rc == PSK_ELIMIT && hp.size() > 1) {   // too many anchors for 32-bit offsets: halve the batch until single pairs
             std::vector<HostPair> todo(hp);
             size_t step = (todo.size() + 1) / 2;
             for (size_t s0 = 0; s0 < todo.size();) {
                 const size_t n1 = std::min(step, todo.size() - s0);
-                rc = chain_batch(ctx, todo.data() + s0, (uint32_t)n1, o, out + b + s0, sw);
+                rc = chain_batch(ctx, todo.data() + s0, (uint32_t)n1, o, out + b + s0, sw, ci, ci ? ci_lo + b + s0 : nullptr, ci ? ci_hi + b + s0 : nullptr);
                 if (rc == PSK_ELIMIT && n1 > 1) { step = (n1 + 1) / 2; continue; }
                 if (rc != PSK_OK) return rc;
                 s0 += n1;
@@ -697,10 +720,10 @@ psk_status chain_pairs_impl(Lane* ctx, const psk_sketch* const* refs, const psk_
 }
 
 psk_status chain_impl(Lane* ctx, const psk_sketch* const* refs, uint32_t n_refs, const psk_sketch* q,
-                      const psk_query_opts* o, psk_hit* out) {
+                      const psk_query_opts* o, psk_hit* out, const psk_ci_opts* ci, float* ci_lo, float* ci_hi) {
     if (!q) { psk_set_error("chain: NULL query"); return PSK_EINVAL; }
     std::vector<const psk_sketch*> qs(n_refs, q);
-    PSK_TRY(chain_pairs_impl(ctx, refs, qs.data(), n_refs, o, out));
+    PSK_TRY(chain_pairs_impl(ctx, refs, qs.data(), n_refs, o, out, ci, ci_lo, ci_hi));
     for (uint32_t i = 0; i < n_refs; i++) out[i].ref_index = i;
     return PSK_OK;
 }

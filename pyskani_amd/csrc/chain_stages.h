@@ -3,6 +3,7 @@
 //   dp.hip       banded chaining DP per chunk, candidate chains
 //   select.hip   greedy selection of non-overlapping chains per pair
 //   reduce.hip   per-pair ANI / aligned fractions
+//   interval.hip bootstrap interval of every pair's ANI (only for the calls that ask for it)
 //   chain.hip    the host side: scratch layout, the launch sequence (chain_run), retries
 // Kernels are declared here and launched from chain.hip; every stage file holds its own device helpers (no relocatable device code).
 #pragma once
@@ -176,6 +177,19 @@ constexpr int RED_SMALL = 1024;
 // groups of 64 chunk rows one wave reduces (pair_reduce_wave_kernel)
 constexpr int RW_PER = 8;      // 512 rows: a 5 Mb genome has ~250 chunks, and the pairs just past 256 rows took a workgroup each (15 of the 19 ms of reduction per 10 000 x 10 000 step)
 
+// ---- bootstrap intervals (interval.hip; the rule: include/pyskani_amd.h psk_ci_opts)
+// (the draw stream and the ranks: common.h ci_draw / ci_ranks, shared with the host)
+struct IntervalArgs {
+    const ChunkOut* chunks; const uint32_t* n_chunks; const uint32_t* cbase;
+    const uint32_t* live; const uint32_t* n_live;   // pairs with a chunk table (null: every pair is visited)
+    const psk_hit* hits;                            // the batch's records: ani_raw < 0 -> (-1, -1); learned -> the bounds move with ani
+    float2* out;                                    // (lo, hi) per pair
+    double* big_vals;                               // one double per chunk-table row: the values of pairs with more than RED_CAP kept chunks
+    unsigned long long* work;                       // [0] += pairs that got bounds, [1] += draws
+    int k; uint32_t B, b_pad, lo_rank, hi_rank; uint64_t seed;
+};
+void interval_launch(const IntervalArgs& A, uint32_t n_pairs, uint32_t rows_pair_max, bool use_live, std::atomic<uint64_t>* tier_launches, hipStream_t st);
+
 struct IsLivePair { const uint32_t* nch; __host__ __device__ bool operator()(const uint32_t& p) const { return nch[p] != 0; } };
 
 struct GsiJoinArgs {
@@ -290,5 +304,9 @@ __global__ __launch_bounds__(256) void pair_reduce_wave_kernel(ReduceArgs R, uin
 __global__ __launch_bounds__(256) void pair_reduce_kernel(ReduceArgs R, uint32_t n_pairs);
 __global__ __launch_bounds__(256) void pair_reduce_large_kernel(ReduceArgs R, uint32_t n_pairs);
 __global__ __launch_bounds__(256) void pair_ref_keys_kernel(const uint2* __restrict__ pair_qr, uint32_t n_pairs, uint32_t* __restrict__ keys, uint32_t* __restrict__ ids);
+__global__ __launch_bounds__(256) void interval_empty_kernel(IntervalArgs A, uint32_t n_pairs);
+__global__ __launch_bounds__(256) void interval_wave_kernel(IntervalArgs A, uint32_t n_pairs);
+__global__ __launch_bounds__(256) void interval_group_kernel(IntervalArgs A, uint32_t n_pairs);
+__global__ __launch_bounds__(256) void interval_global_kernel(IntervalArgs A, uint32_t n_pairs);
 template <bool EMIT>
 __global__ __launch_bounds__(64) void gsi_join_kernel(GsiJoinArgs A);

@@ -87,8 +87,8 @@ struct Scratch {
 };
 
 // kernels whose launches can be bracketed by HIP events on the ctx stream (psk_ctx_timing)
-enum KernelId { K_SKETCH_SCAN = 0, K_SKETCH_EMIT, K_SKETCH_SORT, K_SCREEN, K_ANCHOR, K_CHAIN_CHUNK, K_SELECT, K_PAIR_REDUCE, K_ANCHOR_EMIT, K_COUNT };
-static const char* const KERNEL_NAMES[K_COUNT] = {"sketch_scan", "sketch_emit", "sketch_sort", "screen", "anchor", "chain_chunk", "select", "pair_reduce", "anchor_emit"};
+enum KernelId { K_SKETCH_SCAN = 0, K_SKETCH_EMIT, K_SKETCH_SORT, K_SCREEN, K_ANCHOR, K_CHAIN_CHUNK, K_SELECT, K_PAIR_REDUCE, K_ANCHOR_EMIT, K_INTERVAL, K_COUNT };
+static const char* const KERNEL_NAMES[K_COUNT] = {"sketch_scan", "sketch_emit", "sketch_sort", "screen", "anchor", "chain_chunk", "select", "pair_reduce", "anchor_emit", "interval"};
 struct TimerRec { int id; hipEvent_t a, b; };
 
 // One GPU (the public psk_ctx handle): the HBM block pool and the execution lanes. A LANE is what a call runs on: its own HIP
@@ -120,6 +120,8 @@ struct psk_ctx {
     std::atomic<uint64_t> cl_edges{0}, cl_rounds{0}, cl_hooks{0};
     // the linkage forest's last call that reached the device (cluster.hip; psk_ctx_forest_stats): undirected edges, rounds that hooked a component, pointer-jump launches
     std::atomic<uint64_t> fo_edges{0}, fo_rounds{0}, fo_jumps{0};
+    // bootstrap intervals (interval.hip; psk_ctx_interval_stats): pairs that got bounds and draws made, summed over the completed batches; launches of the three tiers
+    std::atomic<uint64_t> ci_pairs{0}, ci_draws{0}, ci_tier[3] = {};
     // lanes: created on demand, at most max_lanes; a call takes a free one (LaneGuard) and gives it back
     std::mutex lanes_mu;
     std::condition_variable lanes_cv;
@@ -607,7 +609,7 @@ struct SmallQSketch {      // device arrays of the query's sketch (lane-owned, r
 psk_status small_query_sketch_enqueue(Lane* ctx, const psk_params* p, const SmallQSketch& A, hipStream_t st);
 
 // ---- shared device helpers ----
-__device__ __forceinline__ uint64_t mm_hash64(uint64_t key) {
+__host__ __device__ __forceinline__ uint64_t mm_hash64(uint64_t key) {
     key = ~(key + (key << 21));
     key = key ^ key >> 24;
     key = (key + (key << 3)) + (key << 8);
@@ -616,6 +618,23 @@ __device__ __forceinline__ uint64_t mm_hash64(uint64_t key) {
     key = key ^ key >> 28;
     key = key + (key << 31);
     return key;
+}
+
+// ---- bootstrap intervals (interval.hip; the rule: include/pyskani_amd.h psk_ci_opts)
+constexpr uint32_t CI_DEFAULT_ITER = 100, CI_MIN_ITER = 20, CI_MAX_ITER = 1024;
+// the draw stream: resample b, draw j of m -> mm_hash64(seed + (b << 32) + (j >> 1)), its low word for an even j, its high word for an odd one, scaled to [0, m).
+// One hash per two draws: 64-bit multiplies and shifts are what the hash costs. Host and device share these lines (psk_ci_draw, the kernels).
+__host__ __device__ __forceinline__ uint64_t ci_key(uint64_t seed, uint32_t b) { return seed + ((uint64_t)b << 32); }
+__host__ __device__ __forceinline__ uint64_t ci_hash(uint64_t key, uint32_t half) { return mm_hash64(key + half); }
+__host__ __device__ __forceinline__ uint32_t ci_index(uint32_t w, uint32_t m) { return (uint32_t)(((uint64_t)w * m) >> 32); }
+__host__ __device__ inline uint32_t ci_draw(uint64_t seed, uint32_t b, uint32_t j, uint32_t m) {
+    const uint64_t h = ci_hash(ci_key(seed, b), j >> 1);
+    return ci_index((j & 1u) ? (uint32_t)(h >> 32) : (uint32_t)h, m);
+}
+// resamples and the ranks of the two bounds among their means in ascending order: the 5 % and 95 % points
+__host__ __device__ inline void ci_ranks(uint32_t iterations, uint32_t* n, uint32_t* lo_rank, uint32_t* hi_rank) {
+    const uint32_t B = iterations ? iterations : CI_DEFAULT_ITER;
+    *n = B; *lo_rank = B / 20; *hi_rank = B - 1 - B / 20;
 }
 
 // mm_hash64 of a key below 2^32 (k <= 16), arranged for gfx950's VALU: there 32-bit add/sub/and/or/xor/not/mov and
@@ -660,8 +679,9 @@ psk_status ensure_probe(Lane* ctx, const psk_sketch* const* refs, uint32_t n);
 __device__ __forceinline__ uint32_t probe_line(uint32_t km, uint32_t lines) { return __umulhi(km * 2654435761u, lines); }
 psk_status screen_impl(Lane* ctx, psk_db* db, const psk_sketch* query, double screen_val, int rescue_small,
                        uint8_t* pass, uint32_t* shared);
+// ci (null: no intervals): the bootstrap bounds of every pair into ci_lo[] / ci_hi[]
 psk_status chain_pairs_impl(Lane* ctx, const psk_sketch* const* refs, const psk_sketch* const* queries, uint32_t n,
-                            const psk_query_opts* o, psk_hit* out);
+                            const psk_query_opts* o, psk_hit* out, const psk_ci_opts* ci = nullptr, float* ci_lo = nullptr, float* ci_hi = nullptr);
 // growing array of hits in malloc'd memory: what the query entry points hand to the caller (psk_free) without another copy
 // Large hit arrays (>= 8 MB) come from hit_block_alloc and go back through hit_block_free (psk_free routes them there): 2 MB-aligned,
 // advised as huge pages, and the last one released is kept for the next call - a 600 MB result is 150 000 first-touch page faults and
@@ -698,6 +718,7 @@ struct HitListT {
     H* release() { H* q = p; p = nullptr; n = cap = 0; return q; }
 };
 using HitList = HitListT<psk_hit>;
+using HitListCi = HitListT<psk_hit_ci>;        // psk_query_many_ci: psk_hit_min and the bootstrap bounds
 using HitListMin = HitListT<psk_hit_min>;      // the 20-byte records of psk_query_many_min: what the reference's Hit holds (hit.rs:77-104)
 // Database.query for n_queries sketches (lib.rs:569-659): hits of query i are all[offsets[i] .. offsets[i+1]), ref insertion order
 // keys (n_queries entries, or null) / ref_base: triangle mode - the pair (query i, reference r) is chained iff keys[i] < 0 or ref_base + r > keys[i] (pass_triangle_kernel)
@@ -706,8 +727,11 @@ psk_status query_many_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queri
 // ... the same with psk_hit_min records (query = index of the query within the call | learned << 31)
 psk_status query_many_min_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o,
                                HitListMin& all, uint64_t* offsets, const int64_t* keys = nullptr, uint64_t ref_base = 0);
+// ... with psk_hit_ci records: the bootstrap interval of every hit's ANI (ci: iterations and seed, resolved by the caller)
+psk_status query_many_ci_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o, const psk_ci_opts* ci,
+                              HitListCi& all, uint64_t* offsets, const int64_t* keys = nullptr, uint64_t ref_base = 0);
 psk_status chain_impl(Lane* ctx, const psk_sketch* const* refs, uint32_t n_refs,
-                      const psk_sketch* query, const psk_query_opts* o, psk_hit* out);
+                      const psk_sketch* query, const psk_query_opts* o, psk_hit* out, const psk_ci_opts* ci = nullptr, float* ci_lo = nullptr, float* ci_hi = nullptr);
 // Database.query from host bytes (lib.rs:549-660 with the _sketch call inside it): the one-launch-sequence path for a small genome
 // (small_query.hip; *done = false: not eligible or a capacity was exceeded - the caller takes psk_sketch_host + query_many_impl)
 constexpr uint32_t SQ_MAX_REFS = 24 * 1024;      // the screen workgroup keeps one shared-marker counter per reference in LDS

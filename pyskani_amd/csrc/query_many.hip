@@ -198,12 +198,35 @@ template <> struct HitRec<psk_hit_min> {
     static uint32_t local_query(const psk_hit_min& h) { return h.query & 0x7FFFFFFFu; }
     static void finish(psk_hit_min& h, uint32_t q) { h.query = (h.query & 0x80000000u) | q; }      // the query's index within the call
 };
+// psk_hit_ci: the record needs the pair's bounds beside its psk_hit, so it is made from the pair's INDEX (RecSource below) and always on the device
+template <> struct HitRec<psk_hit_ci> {
+    __host__ __device__ static psk_hit_ci from_raw(const psk_hit& r, float lo = -1.0f, float hi = -1.0f) {
+        psk_hit_ci m; m.ani = r.ani; m.af_query = r.af_query; m.af_ref = r.af_ref; m.ref_index = r.ref_index; m.query = r.reserved | (r.learned ? 0x80000000u : 0u); m.ci_lo = lo; m.ci_hi = hi; return m;
+    }
+    static uint32_t local_query(const psk_hit_ci& h) { return h.query & 0x7FFFFFFFu; }
+    static void finish(psk_hit_ci& h, uint32_t q) { h.query = (h.query & 0x80000000u) | q; }
+};
 template <class H> struct ToRec { __host__ __device__ H operator()(const psk_hit& r) const { return HitRec<H>::from_raw(r); } };
+// what the ani > 0.1 selection reads: the batch's psk_hit records converted on their way through it
+template <class H> struct RecSource {
+    static constexpr bool device_only = false;
+    using It = hipcub::TransformInputIterator<H, ToRec<H>, const psk_hit*>;
+    static It make(const ChainBufs& L) { return It(L.hits, ToRec<H>()); }
+};
+struct ToRecCi {
+    const psk_hit* hits; const float2* ci;
+    __host__ __device__ psk_hit_ci operator()(const uint32_t& p) const { const float2 b = ci[p]; return HitRec<psk_hit_ci>::from_raw(hits[p], b.x, b.y); }
+};
+template <> struct RecSource<psk_hit_ci> {
+    static constexpr bool device_only = true;      // (the small batch's host-side filter copies raw psk_hit records: no bounds among them)
+    using It = hipcub::TransformInputIterator<psk_hit_ci, ToRecCi, hipcub::CountingInputIterator<uint32_t>>;
+    static It make(const ChainBufs& L) { return It(hipcub::CountingInputIterator<uint32_t>(0), ToRecCi{L.hits, L.ci}); }
+};
 template <class H> struct RecPasses { __host__ __device__ bool operator()(const H& h) const { return h.ani > 0.1f; } };   // lib.rs:654
 
 template <class H>
 static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o,
-                               HitListT<H>& all, uint64_t* offsets, const int64_t* keys, uint64_t ref_base) {
+                               HitListT<H>& all, uint64_t* offsets, const int64_t* keys, uint64_t ref_base, const psk_ci_opts* ci = nullptr) {
     hipStream_t st = ctx->stream;
     offsets[0] = 0;
     const Switches sw = Switches::read();      // ($PSK_*: once per call; the helper threads of the two-lane mode read this copy)
@@ -612,7 +635,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                     std::vector<BatchQ> bqs; std::vector<uint2> tab, ebase; std::vector<uint32_t> qn;      // (host copies feed asynchronous copies: alive until the job is reaped)
                     uint64_t pairs = 0, items = 0, rows = 0, rows_pair_max = 0;
                     psk_status rc = PSK_OK; bool refit = false; char err[512] = "";
-                    std::vector<H> hits; uint64_t anchors = 0, cands = 0, wrows = 0, visited = 0, lookups = 0; uint32_t misc[16] = {};
+                    std::vector<H> hits; uint64_t anchors = 0, cands = 0, wrows = 0, visited = 0, lookups = 0, ci_pairs = 0, ci_draws = 0; uint32_t misc[16] = {};
                 };
                 PipeJob job[2];
                 std::thread th[2];
@@ -629,7 +652,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                         hipStream_t s2 = ln->stream;
                         const uint32_t n_pairs = (uint32_t)J.pairs;
                         ChainBufs L;
-                        psk_status lrc = chain_layout(ln, n_pairs, (size_t)J.items, (size_t)J.rows, J.bqs.size(), &L);
+                        psk_status lrc = chain_layout(ln, n_pairs, (size_t)J.items, (size_t)J.rows, J.bqs.size(), &L, ci != nullptr);
                         if (lrc == PSK_ENOMEM) { J.refit = true; ctx->dev->rr_refit++; return PSK_OK; }
                         PSK_TRY(lrc);
                         L.rows_pair_max = (uint32_t)std::min<uint64_t>(J.rows_pair_max, 0xFFFFFFFFu);
@@ -655,7 +678,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                         L.gsl_cnt = (uint32_t*)(Jb + o_cnt); L.gsl_rec = (uint4*)(Jb + o_rec); L.gsl_bm = (uint32_t*)(Jb + o_bm);
                         PSK_HIP(hipMemcpyAsync(L.bq, J.bqs.data(), sizeof(BatchQ) * J.bqs.size(), hipMemcpyHostToDevice, s2));
                         hipLaunchKernelGGL(pair_build_rows_kernel, dim3((uint32_t)J.bqs.size()), dim3(256), 0, s2, L.bq, d_pass, n, d_qd, d_rd, L.pairs, L.sbase, L.cbase, L.pair_qr, n_pairs, (uint32_t)J.items, (uint32_t)J.rows);
-                        const bool host_filter = n_pairs <= 4096;
+                        const bool host_filter = !RecSource<H>::device_only && n_pairs <= 4096;
                         H* d_sel = nullptr;
                         if (!host_filter) { lrc = ln->q_sel.reserve(al256(sizeof(H) * (size_t)n_pairs + 256)); if (lrc == PSK_ENOMEM) { J.refit = true; ctx->dev->rr_refit++; return PSK_OK; } PSK_TRY(lrc); d_sel = (H*)ln->q_sel.p; }
                         void* hp = nullptr;
@@ -665,16 +688,16 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                         cap = std::min<uint64_t>(cap, std::max<uint64_t>(ln->q_d.cap / (4 * CHAIN_ANCHOR_WORDS) > 128 ? ln->q_d.cap / (4 * CHAIN_ANCHOR_WORDS) - 128 : 0, (uint64_t)J.items / 4 * 3 + 65536));
                         bool wide = sw.join_wide();
                         for (int attempt = 0;; attempt++) {
-                            psk_status rrc = chain_run(ln, L, n_pairs, (size_t)J.items, (size_t)J.rows, db->params, o, d_qd, d_rd, cap, wide, sw, false);
+                            psk_status rrc = chain_run(ln, L, n_pairs, (size_t)J.items, (size_t)J.rows, db->params, o, d_qd, d_rd, cap, wide, sw, false, ci);
                             if (rrc == PSK_ENOMEM) { (void)hipStreamSynchronize(s2); J.refit = true; ctx->dev->rr_refit++; return PSK_OK; }
                             PSK_TRY(rrc);
                             if (!host_filter) {
                                 size_t tmp3 = 0;
-                                hipcub::TransformInputIterator<H, ToRec<H>, const psk_hit*> rec_it(L.hits, ToRec<H>());
+                                typename RecSource<H>::It rec_it = RecSource<H>::make(L);
                                 PSK_HIP(hipcub::DeviceSelect::If(nullptr, tmp3, rec_it, d_sel, L.misc + 12, (int)n_pairs, RecPasses<H>(), s2));
                                 PSK_TRY(ln->q_c.reserve(tmp3));
                                 PSK_HIP(hipcub::DeviceSelect::If(ln->q_c.p, tmp3, rec_it, d_sel, L.misc + 12, (int)n_pairs, RecPasses<H>(), s2));
-                                PSK_HIP(hipMemcpyAsync(T, L.misc, sizeof(ChainTail), hipMemcpyDeviceToHost, s2));
+                                PSK_HIP(hipMemcpyAsync(T, L.misc, ci ? sizeof(ChainTailCi) : sizeof(ChainTail), hipMemcpyDeviceToHost, s2));
                             } else PSK_HIP(hipMemcpyAsync(T, L.misc, 256 + sizeof(psk_hit) * (size_t)n_pairs, hipMemcpyDeviceToHost, s2));
                             PSK_HIP(hipStreamSynchronize(s2));
                             bool retry, was_wide = wide;
@@ -694,6 +717,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                             PSK_HIP(hipStreamSynchronize(s2));
                             J.hits.assign(h_sel, h_sel + n_sel);
                         }
+                        if (ci) { J.ci_pairs = ((const ChainTailCi*)T)->ci_pairs; J.ci_draws = ((const ChainTailCi*)T)->ci_draws; }
                         J.anchors = T->total64; J.cands = T->cands; J.wrows = T->rows; J.visited = T->visited; memcpy(J.misc, T->misc, sizeof J.misc);
                         J.lookups = 0; for (const BatchQ& e : J.bqs) J.lookups += h_qd[e.q].n;
                         return PSK_OK;
@@ -721,6 +745,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                     }
                     ctx->dev->w_pairs += J.pairs; ctx->dev->w_items += J.items; ctx->dev->w_anchors += J.anchors; ctx->dev->w_cands += J.cands; ctx->dev->w_rows += J.wrows; count_tier_pairs(ctx->dev, J.misc);
                     ctx->dev->w_lookups += J.lookups; ctx->dev->w_visited += J.visited;
+                    if (ci) { ctx->dev->ci_pairs += J.ci_pairs; ctx->dev->ci_draws += J.ci_draws; }
                     return PSK_OK;
                 };
                 uint32_t k = 0;
@@ -790,7 +815,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                 // nothing to chain (queries without seeds): no hits
             } else {
                 ChainBufs L;
-                psk_status lrc = chain_layout(ctx, n_pairs, (size_t)items, (size_t)rows, bqs.size(), &L);
+                psk_status lrc = chain_layout(ctx, n_pairs, (size_t)items, (size_t)rows, bqs.size(), &L, ci != nullptr);
                 L.rows_pair_max = (uint32_t)std::min<uint64_t>(rows_pair_max, 0xFFFFFFFFu);
                 if (round_gsi) {
                     if (round_slice) { L.g_key = (const uint32_t*)db->bsi_key.p; L.g_val = (const unsigned long long*)db->bsi_val.p; L.g_bucket = (const uint32_t*)db->bsi_bucket.p; L.g_shift = db->bsi_shift; L.g_nb1 = db->bsi_nb1; L.g_blocks = db->bsi_blocks; L.g_base = (const unsigned long long*)db->bsi_base.p; L.g_tagged = db->bsi_tagged; }
@@ -828,7 +853,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                 // a small batch: status and every record in one copy; a large one: the status alone is waited for, the selected hits then cross on the copy
                 // stream WHILE THE NEXT BATCH COMPUTES (600 MB per metagenome step: 15 ms of copies that kept the compute queues idle), out of one of two
                 // device halves so that the next batch's selection does not write what is still being read
-                const bool host_filter = n_pairs <= 4096;
+                const bool host_filter = !RecSource<H>::device_only && n_pairs <= 4096;
                 H* d_sel = nullptr;
                 if (!host_filter) {
                     PSK_TRY(ctx->copy_lane(&cst));
@@ -848,19 +873,19 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                 for (int attempt = 0;; attempt++) {
                     struct timespec tb0{}, tb1{}, tb2{};
                     if (trace_batch) clock_gettime(CLOCK_MONOTONIC, &tb0);
-                    psk_status rrc = chain_run(ctx, L, n_pairs, (size_t)items, (size_t)rows, db->params, o, d_qd, ref_descs(), cap, wide, sw, round_probe && !round_gsi);
+                    psk_status rrc = chain_run(ctx, L, n_pairs, (size_t)items, (size_t)rows, db->params, o, d_qd, ref_descs(), cap, wide, sw, round_probe && !round_gsi, ci);
                     if (trace_batch) clock_gettime(CLOCK_MONOTONIC, &tb1);
                     if (rrc == PSK_ENOMEM && n_pairs > 1 && max_items > (1ull << 22)) { (void)hipStreamSynchronize(st); ctx->huge_release(); too_big = true; break; }
                     PSK_TRY(rrc);
                     if (!host_filter) {      // (the ani > 0.1 filter of a small batch runs on the host: three launches fewer)
                         size_t tmp3 = 0;
-                        hipcub::TransformInputIterator<H, ToRec<H>, const psk_hit*> rec_it(L.hits, ToRec<H>());      // (the record that crosses is made here)
+                        typename RecSource<H>::It rec_it = RecSource<H>::make(L);      // (the record that crosses is made here)
                         PSK_HIP(hipcub::DeviceSelect::If(nullptr, tmp3, rec_it, d_sel, L.misc + 12, (int)n_pairs, RecPasses<H>(), st));
                         PSK_TRY(ctx->q_c.reserve(tmp3));
                         PSK_HIP(hipcub::DeviceSelect::If(ctx->q_c.p, tmp3, rec_it, d_sel, L.misc + 12, (int)n_pairs, RecPasses<H>(), st));   // order-preserving: hits stay in (query, ref) order
                     }
                     if (host_filter) PSK_HIP(hipMemcpyAsync(T, L.misc, 256 + sizeof(psk_hit) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));      // status, anchor total, hits: one copy
-                    else PSK_HIP(hipMemcpyAsync(T, L.misc, sizeof(ChainTail), hipMemcpyDeviceToHost, st));
+                    else PSK_HIP(hipMemcpyAsync(T, L.misc, ci ? sizeof(ChainTailCi) : sizeof(ChainTail), hipMemcpyDeviceToHost, st));
                     PSK_TRY(consume());                     // the previous batch's hits, while this one runs
                     PSK_HIP(hipStreamSynchronize(st));      // the ONE synchronisation of a batch
                     if (trace_batch) {
@@ -881,6 +906,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                     if (!retry && L.gsi_onepass && (T->misc[0] & 4u)) { L.gsi_onepass = false; retry = true; ctx->dev->rr_onepass++; }      // a pair with more anchors than query seeds: with the count pass
                     if (!retry) {
                         ctx->dev->w_pairs += n_pairs; ctx->dev->w_items += items; ctx->dev->w_anchors += T->total64; ctx->dev->w_cands += T->cands; ctx->dev->w_rows += T->rows; count_tier_pairs(ctx->dev, T->misc);
+                        if (ci) count_interval(ctx->dev, T);
                         if (round_gsi) { uint64_t lk = 0; for (const BatchQ& e : bqs) lk += h_qd[e.q].n; ctx->dev->w_lookups += lk; ctx->dev->w_visited += T->visited; }
                         break;
                     }
@@ -888,7 +914,7 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
                 }
                 if (too_big) { max_items = std::max<uint64_t>(1, items / 4); max_pairs = std::max<uint64_t>(1, pairs / 4); continue; }   // repeat-rich: plan smaller batches from the same position
                 n_sel = T->misc[12];
-                if (n_pairs <= 4096) {      // host-side filter of a small batch (lib.rs:654), order kept; the raw records become H where they stand (H is no larger)
+                if (host_filter) {      // host-side filter of a small batch (lib.rs:654), order kept; the raw records become H where they stand (H is no larger)
                     const psk_hit* raw = (const psk_hit*)((char*)hpin + 256);
                     uint32_t w = 0;
                     for (uint32_t i = 0; i < n_pairs; i++) { const psk_hit r = raw[i]; if (r.ani > 0.1f) h_sel[w++] = HitRec<H>::from_raw(r); }
@@ -916,6 +942,10 @@ static psk_status query_many_t(Lane* ctx, psk_db* db, const psk_sketch* const* q
 }
 psk_status query_many_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o, HitList& all, uint64_t* offsets, const int64_t* keys, uint64_t ref_base) {
     return query_many_t<psk_hit>(ctx, db, queries, n_queries, o, all, offsets, keys, ref_base);
+}
+psk_status query_many_ci_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o, const psk_ci_opts* ci, HitListCi& all, uint64_t* offsets, const int64_t* keys, uint64_t ref_base) {
+    if (!ci) { psk_set_error("internal: query_many_ci without options"); return PSK_EINVAL; }
+    return query_many_t<psk_hit_ci>(ctx, db, queries, n_queries, o, all, offsets, keys, ref_base, ci);
 }
 psk_status query_many_min_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, const psk_query_opts* o, HitListMin& all, uint64_t* offsets, const int64_t* keys, uint64_t ref_base) {
     return query_many_t<psk_hit_min>(ctx, db, queries, n_queries, o, all, offsets, keys, ref_base);

@@ -98,14 +98,19 @@ struct ChainBufs {
     const uint8_t* d_pass = nullptr; uint32_t n_refs = 0, n_bq = 0, p_cap = 0;
     // mid-sized pairs (all-vs-all of genomes): the index join by (query, slice) waves (slice_join.hip); the batch's wave table, record offsets and per-record arrays
     bool gsi_slice = false; const uint2* gsl_tab = nullptr; uint32_t gsl_n_tab = 0; const uint2* gsl_ebase = nullptr; uint32_t *gsl_cnt = nullptr, *gsl_bm = nullptr, *gsl_un = nullptr, gsl_n_slices = 0; uint4* gsl_rec = nullptr;
+    float2* ci = nullptr;          // bootstrap bounds per pair, behind everything else (chain_layout with want_ci; null: the call asked for no intervals)
     bool gsi_onepass = false;      // the index join without its COUNT pass (GsiJoinArgs::onepass): asked for by the caller, which reruns the batch without it when err bit 2 comes back
 };
-psk_status chain_layout(Lane* ctx, size_t n_pairs, size_t n_items, size_t n_rows, size_t n_bq, ChainBufs* L);
+// want_ci / ci: the bootstrap intervals (interval.hip). Off (the default), layout, launches and output are what they are without the feature.
+psk_status chain_layout(Lane* ctx, size_t n_pairs, size_t n_items, size_t n_rows, size_t n_bq, ChainBufs* L, bool want_ci = false);
 psk_status chain_run(Lane* ctx, const ChainBufs& L, uint32_t n_pairs, size_t n_items, size_t n_rows, const psk_params& prm,
-                     const psk_query_opts* o, const SketchDesc* d_qd, const SketchDesc* d_rd, uint64_t cap, bool wide, const Switches& sw, bool probe_ok = false);
+                     const psk_query_opts* o, const SketchDesc* d_qd, const SketchDesc* d_rd, uint64_t cap, bool wide, const Switches& sw, bool probe_ok = false,
+                     const psk_ci_opts* ci = nullptr);
 uint64_t anchor_cap_for(Lane* ctx, size_t n_items, bool sparse = false, bool gb_scale = false);
 // outcome of a launch sequence, read back with the hits
 struct ChainTail { uint32_t misc[16]; unsigned long long total64, visited, cands, rows; };      // (misc[16..23]: the anchor total; index entries the join visited; with the timers on, candidates and live chunk rows)
+struct ChainTailCi : ChainTail { unsigned long long ci_pairs, ci_draws; };      // (misc[24..27]: pairs that got bounds, draws - read back only by the calls that asked for intervals)
+static inline void count_interval(psk_ctx* dev, const ChainTail* T) { const ChainTailCi* C = (const ChainTailCi*)T; dev->ci_pairs += C->ci_pairs; dev->ci_draws += C->ci_draws; }
 psk_status chain_check(const ChainTail& T, uint32_t n_pairs, uint64_t* cap, bool* wide, bool* retry);
 // psk_ctx_rerun_stats: what chain_check asked for after an attempt in the format `was_wide` (counted, never read back)
 static inline void count_rerun(psk_ctx* dev, bool was_wide, bool wide, bool retry) { if (wide && !was_wide) dev->rr_wide++; else if (retry) dev->rr_cap++; }
@@ -113,7 +118,8 @@ static inline void count_rerun(psk_ctx* dev, bool was_wide, bool wide, bool retr
 // (misc[13]), the first wave tier passed to the second (misc[14]) and the second to the workgroup tier (misc[10])
 static inline void count_tier_pairs(psk_ctx* dev, const uint32_t* misc) { dev->tier[TIER_PAIRS_LIVE] += misc[9]; dev->tier[TIER_PAIRS_REST] += misc[13]; dev->tier[TIER_PAIRS_MID] += misc[14]; dev->tier[TIER_PAIRS_BIG] += misc[10]; }
 struct HostPair { const psk_sketch* r; const psk_sketch* q; };
-psk_status chain_batch(Lane* ctx, const HostPair* hp, uint32_t n_pairs, const psk_query_opts* o, psk_hit* out, const Switches& sw);
+psk_status chain_batch(Lane* ctx, const HostPair* hp, uint32_t n_pairs, const psk_query_opts* o, psk_hit* out, const Switches& sw,
+                       const psk_ci_opts* ci = nullptr, float* ci_lo = nullptr, float* ci_hi = nullptr);
 
 // ---- query_many.hip
 uint64_t index_stamp(const psk_db* db);

@@ -164,6 +164,52 @@ def _hit_restore(fields):
     return _HIT_BASE.__new__(Hit, *fields)
 
 
+class IntervalHit(Hit):
+    """A `Hit` with the bootstrap confidence interval of its `identity` (skani's --ci; `Database.query_ci`): `identity_low` and `identity_high`, the 5 % and
+    95 % points of the identity over resamples of the per-chunk estimates whose mean it is. Read-only like the fields of `Hit`."""
+
+    __slots__ = ("_ci",)
+
+    def __new__(cls, identity, query_name, query_fraction, reference_name, reference_fraction, identity_low, identity_high):
+        self = super().__new__(cls, identity, query_name, query_fraction, reference_name, reference_fraction)
+        lo, hi = float(np.float32(identity_low)), float(np.float32(identity_high))
+        if not lo <= hi:
+            raise ValueError(f"Invalid interval: identity_low {lo} > identity_high {hi}")
+        object.__setattr__(self, "_ci", (lo, hi))
+        return self
+
+    @classmethod
+    def _from_ci_records(cls, recs, qname, names):
+        """[IntervalHit] from psk_hit_ci records (values valid by construction: no range checks)"""
+        out = []
+        for ani, afq, ri, afr, q, lo, hi in zip(recs["ani"].tolist(), recs["af_query"].tolist(), recs["ref_index"].tolist(), recs["af_ref"].tolist(),
+                                                recs["query"].tolist(), recs["ci_lo"].tolist(), recs["ci_hi"].tolist()):
+            h = _HIT_BASE.__new__(cls, ani, qname, afq, names[ri], afr, bool(q >> 31))
+            object.__setattr__(h, "_ci", (lo, hi))
+            out.append(h)
+        return out
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"attribute '{name}' of 'IntervalHit' objects is not writable")
+
+    identity_low = property(lambda self: self._ci[0])
+    identity_high = property(lambda self: self._ci[1])
+
+    def __repr__(self):
+        return ("IntervalHit(identity={!r}, query_name={!r}, query_fraction={!r}, reference_name={!r}, reference_fraction={!r}, "
+                "identity_low={!r}, identity_high={!r})").format(self.identity, self.query_name, self.query_fraction, self.reference_name,
+                                                                 self.reference_fraction, self.identity_low, self.identity_high)
+
+    def __reduce__(self):
+        return (_interval_hit_restore, ((self.identity, self.query_name, self.query_fraction, self.reference_name, self.reference_fraction, self.learned), self._ci))
+
+
+def _interval_hit_restore(fields, ci):
+    h = _HIT_BASE.__new__(IntervalHit, *fields)
+    object.__setattr__(h, "_ci", tuple(ci))
+    return h
+
+
 class Sketch:
     """A sketched genome resident in HBM (sketch.rs:4-31)."""
 
@@ -642,6 +688,7 @@ class Database:
 
     _HIT_DTYPE = np.dtype(_capi.Hit)
     _HIT_MIN_DTYPE = np.dtype(_capi.HitMin)
+    _HIT_CI_DTYPE = np.dtype(_capi.HitCi)
 
     def _hit(self, r, qname):
         """One psk_hit (ctypes struct) -> Hit (the lazy path: a handful of hits)."""
@@ -713,6 +760,69 @@ class Database:
                 if hits_p:
                     self._lib.psk_free(hits_p)
         return recs, np.frombuffer(offs, dtype=np.uint64).astype(np.int64)
+
+    def _ci_opts(self, iterations, rng_seed):
+        iterations, rng_seed = operator.index(iterations), operator.index(rng_seed)
+        if iterations != 0 and not 20 <= iterations <= 1024:
+            raise ValueError(f"iterations must be 0 (= 100) or within 20 .. 1024, not {iterations}")
+        if not 0 <= rng_seed < 1 << 64:
+            raise ValueError("rng_seed must be an unsigned 64-bit integer")
+        if not hasattr(self._lib, "psk_query_many_ci"):
+            raise RuntimeError("the loaded library has no interval entry points: rebuild it")
+        return _capi.CiOpts(iterations, 0, rng_seed)
+
+    def query_handles_ci(self, handles, n, *, iterations=100, rng_seed=0, keys=None, ref_base=0, learned_ani=None, cutoff=None, faster_small=False):
+        """`query_handles` with the bootstrap confidence interval of every hit's ANI (skani's --ci; psk_query_many_ci) -> (records, offsets): 28-byte psk_hit_ci
+        records - the fields of psk_hit_min, bit for bit those of `query_handles`, then `ci_lo` and `ci_hi`, the 5 % and 95 % points of the ANI over `iterations`
+        resamples (0 or 100: skani's count; else 20 .. 1024) of the pair's per-chunk estimates - and the n + 1 int64 offsets. `rng_seed` seeds the draw stream; a
+        pair's interval depends on its chunks, `iterations` and `rng_seed` alone. keys / ref_base: the triangle mode of `query_handles`. The interval belongs to
+        the mean estimator: there is no median / robust here."""
+        opts = self._opts(learned_ani, False, False, cutoff, faster_small)
+        ci = self._ci_opts(iterations, rng_seed)
+        c_keys = None
+        if keys is not None:
+            c_keys = np.ascontiguousarray(keys, dtype=np.int64)
+            if c_keys.ndim != 1 or len(c_keys) != n:
+                raise ValueError(f"keys must hold one integer per query: {n} expected, {c_keys.size} given")
+            if int(ref_base) < 0:
+                raise ValueError("ref_base must not be negative")
+        with Database._Borrow(self, False):
+            hits_p = C.POINTER(_capi.HitCi)()
+            offs = (C.c_uint64 * (n + 1))()
+            _capi.check(self._lib.psk_query_many_ci(self._h, handles, n, c_keys.ctypes.data_as(C.POINTER(C.c_int64)) if c_keys is not None else None,
+                                                    int(ref_base) if c_keys is not None else 0, C.byref(opts), C.byref(ci), C.byref(hits_p), offs))
+            try:
+                recs = _capi.hit_records(hits_p, 0, int(offs[n]), self._HIT_CI_DTYPE)
+            finally:
+                if hits_p:
+                    self._lib.psk_free(hits_p)
+        return recs, np.frombuffer(offs, dtype=np.uint64).astype(np.int64)
+
+    def triangle_records_ci(self, *, iterations=100, rng_seed=0, learned_ani=None, cutoff=None, faster_small=False):
+        """`triangle_records` with the interval of every record (psk_hit_ci records, as `query_handles_ci` returns them); the same restrictions: a
+        memory-resident database, no name sketched twice."""
+        if self._n_lazy:
+            raise RuntimeError("triangle_records_ci needs a memory-resident database")
+        n = len(self._names)
+        if len(set(self._names)) != n:
+            raise ValueError("triangle_records_ci: a name was sketched more than once; which sketch of it is the later reference is ambiguous")
+        if n < 2:
+            self._ci_opts(iterations, rng_seed)
+            return np.zeros(0, self._HIT_CI_DTYPE), np.zeros(n + 1, np.int64)
+        return self.query_handles_ci(self.sketch_handles(), n, iterations=iterations, rng_seed=rng_seed, keys=np.arange(n, dtype=np.int64), ref_base=0,
+                                     learned_ani=learned_ani, cutoff=cutoff, faster_small=faster_small)
+
+    def query_ci(self, name, *contigs, seed=True, iterations=100, rng_seed=0, learned_ani=None, cutoff=None, faster_small=False):
+        """`query` returning `IntervalHit`s: every hit with the 5 % - 95 % bootstrap interval of its identity (`identity_low`, `identity_high`; skani's --ci).
+        The genome is sketched without being added, then queried in one psk_query_many_ci call. Needs a memory-resident database."""
+        if not isinstance(name, str):
+            raise TypeError("name must be a str")
+        if self._n_lazy:
+            raise RuntimeError("query_ci needs a memory-resident database")
+        sk = self.sketch_only(name, *contigs, seed=seed)
+        recs, _ = self.query_handles_ci((C.c_void_p * 1)(sk._h), 1, iterations=iterations, rng_seed=rng_seed, learned_ani=learned_ani, cutoff=cutoff,
+                                        faster_small=faster_small)
+        return IntervalHit._from_ci_records(recs, name, self._names)
 
     def triangle_records(self, *, learned_ani=None, median=False, robust=False, cutoff=None, faster_small=False, raw=False):
         """The database's own all-vs-all with every unordered pair chained ONCE and no genome against itself (skani's `triangle`): genome i - insertion index - is the

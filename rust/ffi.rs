@@ -34,6 +34,12 @@ pub struct PskHit {
 /// psk_hit_min: what `Hit` holds (hit.rs:77-104) in 20 bytes; `query` = index of the query within the call, bit 31 = the model produced `ani`
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct PskHitMin { pub ani: f32, pub af_query: f32, pub af_ref: f32, pub ref_index: u32, pub query: u32 }
+/// psk_hit_ci: psk_hit_min and the bootstrap interval of `ani` (psk_query_many_ci)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct PskHitCi { pub ani: f32, pub af_query: f32, pub af_ref: f32, pub ref_index: u32, pub query: u32, pub ci_lo: f32, pub ci_hi: f32 }
+/// psk_ci_opts: iterations 0 = 100, else 20 ..= 1024; reserved must be 0; a null pointer means all zeros
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PskCiOpts { pub iterations: u32, pub reserved: u32, pub seed: u64 }
 /// psk_cluster_opts: min_ani <= 0 means 0.95; min_af < 0 means 0.5, 0 no aligned-fraction condition; af_rule 0 both / 1 either; linkage 0 greedy / 1 single
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct PskClusterOpts { pub min_ani: f64, pub min_af: f64, pub af_rule: i32, pub linkage: i32 }
@@ -155,6 +161,15 @@ extern "C" {
                       pass: *mut u8, shared: *mut u32) -> c_int;
     pub fn psk_chain(ctx: *mut PskCtx, refs: *const *const PskSketch, n: u32, q: *const PskSketch,
                      o: *const PskQueryOpts, out: *mut PskHit) -> c_int;
+    // confidence intervals of the ANI (skani's --ci): the 5 % - 95 % bootstrap interval of every pair. Added after PSK_ABI_VERSION 7 without raising it: look the
+    // symbols up before relying on them when the library may be older. key null: no triangle mask; ci null: 100 resamples, seed 0
+    pub fn psk_chain_ci(ctx: *mut PskCtx, refs: *const *const PskSketch, n: u32, q: *const PskSketch, o: *const PskQueryOpts, ci: *const PskCiOpts,
+                        out: *mut PskHit, ci_lo: *mut f32, ci_hi: *mut f32) -> c_int;
+    pub fn psk_query_many_ci(db: *mut PskDb, qs: *const *const PskSketch, n: u32, key: *const i64, ref_base: u64, o: *const PskQueryOpts, ci: *const PskCiOpts,
+                             hits: *mut *mut PskHitCi, offsets: *mut u64) -> c_int;
+    pub fn psk_ctx_interval_stats(ctx: *mut PskCtx, pairs: *mut u64, draws: *mut u64, tier_launches: *mut u64, reset: c_int) -> c_int;
+    pub fn psk_ci_draw(seed: u64, b: u32, j: u32, m: u32) -> u32;
+    pub fn psk_ci_ranks(iterations: u32, n: *mut u32, lo_rank: *mut u32, hi_rank: *mut u32);
 }
 
 /// psk_status -> the PyErr pyskani already raises for that class of failure
