@@ -117,7 +117,7 @@ const char* psk_version(void);
 /* The C-ABI's revision: raised whenever an entry point's parameters or a structure's layout change (4: psk_sketch_unpack takes the extent of its source buffer as third
  * argument; 5: psk_hit_min / psk_query_many_min / psk_gather_hits_min / psk_ctx_join_work added;
  * 6: psk_db_locality added; 7: psk_ctx_rerun_stats added). psk_query_many_tri and psk_query_many_tri_min came after 7 WITHOUT raising it: no existing argument
- * list or structure moved, and a binding that wants them detects them by their presence (dlsym); psk_cluster_records, psk_ctx_cluster_stats, psk_ctx_tier_stats, psk_cluster_forest, psk_ctx_forest_stats and the interval calls (psk_chain_ci, psk_query_many_ci, psk_ctx_interval_stats, psk_ci_draw, psk_ci_ranks) likewise. A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
+ * list or structure moved, and a binding that wants them detects them by their presence (dlsym); psk_cluster_records, psk_ctx_cluster_stats, psk_ctx_tier_stats, psk_cluster_forest, psk_ctx_forest_stats, psk_screen_many, psk_ctx_screen_stats and the interval calls (psk_chain_ci, psk_query_many_ci, psk_ctx_interval_stats, psk_ci_draw, psk_ci_ranks) likewise. A binding compares psk_abi_version() with the PSK_ABI_VERSION it was
  * written against before it calls anything else: an argument list that moved is a memory error, not a link error. */
 #define PSK_ABI_VERSION 7
 int psk_abi_version(void);
@@ -158,6 +158,11 @@ psk_status psk_ctx_rerun_stats(psk_ctx* ctx, uint64_t* cap, uint64_t* wide, uint
  * (more than 512 candidate chains) and to the workgroup tier (more than 1024). Read-only: no decision depends on them. Added after ABI 7 without raising it: a binding
  * detects it by its presence. */
 psk_status psk_ctx_tier_stats(psk_ctx* ctx, uint64_t* out, int n, int reset);
+/* Measurement: sub-launches of the marker screen since the last reset, by path. out[0..n) receives, in this order (entries beyond the sixth are zero): a workgroup per
+ * pair; sliced queries (marker sets above 65 536); the inverted marker index with the count row in LDS, looked up by waves; the same by one lane per marker; the
+ * inverted index with the count matrix in HBM; the single query's kernel (psk_screen). Read-only: no decision depends on them. Added after ABI 7 without raising it:
+ * a binding detects it by its presence. */
+psk_status psk_ctx_screen_stats(psk_ctx* ctx, uint64_t* out, int n, int reset);
 /* Host-side 2-bit packing of the ingest pipeline (csrc/pack_host.cpp), exposed for tests: n ASCII bases -> ceil(n / 16) words, the first base in a
  * word's highest two bits; A 0, C 1, G 2, T 3, case-insensitive, every other byte 0 (the codes of the sketch kernels). mode 0: the best
  * implementation the CPU has (AVX-512BW), 1: the scalar one. */
@@ -202,7 +207,8 @@ psk_status psk_sketch_export(const psk_sketch* s, psk_seed* seeds, uint64_t* mar
 psk_status psk_sketch_contig_lens(const psk_sketch* s, uint32_t* lens);
 /* Inverse of psk_sketch_export (+ contig lengths): rebuilds a device-resident sketch, e.g. from the records
  * Database.open/load read back (lib.rs:95-122, 249-337). seeds in (contig,pos) order, markers sorted distinct.
- * has_seeds = 0 builds a marker-only sketch (skani::types::Sketch::get_markers_only, lib.rs:495). */
+ * has_seeds = 0 builds a marker-only sketch (skani::types::Sketch::get_markers_only, lib.rs:495).
+ * Markers are 42-bit values (21-mers, two bits a base): one of 2^42 or more is PSK_EINVAL, the message names its index. */
 psk_status psk_sketch_import(psk_ctx* ctx, const psk_params* p, const uint32_t* contig_lens, uint32_t n_contigs,
                              const psk_seed* seeds, uint64_t n_seeds, const uint64_t* markers, uint64_t n_markers,
                              int has_seeds, psk_sketch** out);
@@ -314,6 +320,11 @@ void psk_bsi_plan(int k, uint64_t max_block, uint32_t n_blocks, uint64_t n_entri
  * pass[i] in {0,1}; shared[i] = |markers(q) ∩ markers(ref_i)| (may be NULL). */
 psk_status psk_screen(psk_db* db, const psk_sketch* query, double screen_val, int rescue_small,
                       uint8_t* pass, uint32_t* shared);
+/* The screen step of psk_query_many alone: pass[i * psk_db_size + r] in {0,1} for query i and reference r (a host array of n_queries x psk_db_size bytes, insertion
+ * order), by the path and the sub-launches psk_query_many would take for these queries ($PSK_SCREEN, $PSK_SCREEN_WAVE, $PSK_SCREEN_GLOBAL as there). Nothing behind
+ * the screen runs (no duplicate-name rule, no triangle mask, no seed prefilter), so markers-only sketches are fine. More than 2^30 cells: PSK_ELIMIT. An empty
+ * database or n_queries = 0 writes nothing. Added after ABI 7 without raising it: a binding detects it by its presence. */
+psk_status psk_screen_many(psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, double screen_val, int rescue_small, uint8_t* pass);
 
 /* chain_seeds(ref, query, map_params) for n_refs references against one query. */
 psk_status psk_chain(psk_ctx* ctx, const psk_sketch* const* refs, uint32_t n_refs,

@@ -73,7 +73,7 @@ SYMBOLS = [
     "psk_ctx_synchronize", "psk_pack2bit_host", "psk_ctx_small_query_stats", "psk_ctx_rerun_stats", "psk_ctx_tier_stats", "psk_ctx_set_timing", "psk_ctx_timing", "psk_db_add_batch", "psk_device_alloc", "psk_device_free", "psk_memcpy_h2d",
     "psk_sketch_host", "psk_sketch_many_host", "psk_sketch_batch_device", "psk_sketch_free", "psk_sketch_free_many", "psk_sketch_info",
     "psk_sketch_export", "psk_sketch_contig_lens", "psk_sketch_import", "psk_db_create", "psk_db_destroy", "psk_db_add", "psk_db_size",
-    "psk_db_name", "psk_db_sketch", "psk_db_locality", "psk_db_seed_index_info", "psk_bsi_plan", "psk_screen", "psk_chain", "psk_query", "psk_query_host", "psk_query_many", "psk_query_many_min", "psk_query_many_tri", "psk_query_many_tri_min", "psk_cluster_records", "psk_ctx_cluster_stats", "psk_cluster_forest", "psk_ctx_forest_stats", "psk_gather_hits_min",
+    "psk_db_name", "psk_db_sketch", "psk_db_locality", "psk_db_seed_index_info", "psk_bsi_plan", "psk_screen", "psk_screen_many", "psk_ctx_screen_stats", "psk_chain", "psk_query", "psk_query_host", "psk_query_many", "psk_query_many_min", "psk_query_many_tri", "psk_query_many_tri_min", "psk_cluster_records", "psk_ctx_cluster_stats", "psk_cluster_forest", "psk_ctx_forest_stats", "psk_gather_hits_min",
     "psk_chain_ci", "psk_query_many_ci", "psk_ctx_interval_stats", "psk_ci_draw", "psk_ci_ranks",
     "psk_sketch_pack_size", "psk_sketch_pack", "psk_sketch_unpack", "psk_sketch_pack_many", "psk_ctx_clock_probe", "psk_ctx_work", "psk_ctx_join_work",
     "psk_comm_unique_id", "psk_comm_create", "psk_comm_destroy", "psk_comm_info", "psk_gather_hits", "psk_gather_sketches",
@@ -138,7 +138,10 @@ def load():
     lib.psk_db_sketch.argtypes = [vp, u32]
     lib.psk_db_sketch.restype = vp
     lib.psk_screen.argtypes = [vp, vp, C.c_double, C.c_int, vp, vp]
-    lib.psk_db_locality.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(lib, "psk_screen_many"):      # (came after ABI 7 without raising it: detected by its presence)
+        lib.psk_screen_many.argtypes = [vp, C.POINTER(vp), u32, C.c_double, C.c_int, vp]
+        lib.psk_ctx_screen_stats.argtypes = [vp, C.POINTER(u64), C.c_int, C.c_int]
+    lib.psk_db_locality.argtypes =[vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     if hasattr(lib, "psk_db_seed_index_info"):      # (came after ABI 7 without raising it: detected by its presence)
         lib.psk_db_seed_index_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.psk_bsi_plan.argtypes = [C.c_int, u64, u32, u64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]

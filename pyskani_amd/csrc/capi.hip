@@ -254,6 +254,12 @@ psk_status psk_ctx_tier_stats(psk_ctx* c, uint64_t* out, int n, int reset) {
     if (reset) for (int i = 0; i < TIER_COUNT; i++) c->tier[i] = 0;
     return PSK_OK;
 }
+psk_status psk_ctx_screen_stats(psk_ctx* c, uint64_t* out, int n, int reset) {
+    if (!c || (n > 0 && !out)) { psk_set_error("NULL argument"); return PSK_EINVAL; }
+    for (int i = 0; i < n; i++) out[i] = i < SCREEN_COUNT ? c->screen_path[i].load() : 0;
+    if (reset) for (int i = 0; i < SCREEN_COUNT; i++) c->screen_path[i] = 0;
+    return PSK_OK;
+}
 psk_status psk_ctx_interval_stats(psk_ctx* c, uint64_t* pairs, uint64_t* draws, uint64_t* tier_launches, int reset) {
     if (!c) { psk_set_error("NULL ctx"); return PSK_EINVAL; }
     if (pairs) *pairs = c->ci_pairs.load();
@@ -392,6 +398,9 @@ psk_status psk_sketch_import(psk_ctx* ctx, const psk_params* p, const uint32_t* 
     if (!ctx || !p || !out || (n_contigs && !contig_lens) || (n_seeds && !seeds) || (n_markers && !markers)) { psk_set_error("sketch_import: NULL argument"); return PSK_EINVAL; }
     if (p->k < 1 || p->k > 16 || p->c < 1 || p->marker_c < 1) { psk_set_error("invalid sketch parameters"); return PSK_EINVAL; }
     if (n_seeds >= 0x7FFFFFF0ull || n_markers >= 0x7FFFFFF0ull) { psk_set_error("sketch too large to import"); return PSK_ELIMIT; }
+    // markers are 2 K_MARKER-bit k-mers: the inverted marker index sorts on those bits alone and indexes its bucket table by their top ones (screen.hip)
+    for (uint64_t i = 0; i < n_markers; i++)
+        if (markers[i] >> (2 * K_MARKER)) { psk_set_error("sketch_import: marker %llu is not a %d-bit value", (unsigned long long)i, 2 * K_MARKER); return PSK_EINVAL; }
     *out = nullptr;
     PSK_LANE(lg, ctx);
     Lane* lane = lg.lane;
@@ -519,6 +528,12 @@ psk_status psk_screen(psk_db* db, const psk_sketch* q, double screen_val, int re
     if (!db || !q || !pass) { psk_set_error("screen: NULL argument"); return PSK_EINVAL; }
     PSK_LANE(lg, db->ctx);
     return screen_impl(lg.lane, db, q, screen_val, rescue_small, pass, shared);
+}
+
+psk_status psk_screen_many(psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, double screen_val, int rescue_small, uint8_t* pass) {
+    if (!db || !pass || (!queries && n_queries)) { psk_set_error("screen_many: NULL argument"); return PSK_EINVAL; }
+    PSK_LANE(lg, db->ctx);
+    return screen_many_impl(lg.lane, db, queries, n_queries, screen_val, rescue_small, pass);
 }
 
 psk_status psk_chain(psk_ctx* ctx, const psk_sketch* const* refs, uint32_t n_refs, const psk_sketch* q, const psk_query_opts* o, psk_hit* out) {

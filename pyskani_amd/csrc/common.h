@@ -97,6 +97,9 @@ struct TimerRec { int id; hipEvent_t a, b; };
 struct Lane;
 // psk_ctx_tier_stats: the order of its counters
 enum { TIER_SELECT_TINY = 0, TIER_PAIR_EMPTY, TIER_REDUCE_TINY, TIER_REDUCE_SMALL, TIER_REDUCE_WAVE, TIER_REDUCE_GROUP, TIER_REDUCE_LARGE, TIER_PAIRS_LIVE, TIER_PAIRS_REST, TIER_PAIRS_MID, TIER_PAIRS_BIG, TIER_COUNT };
+// psk_ctx_screen_stats: the order of its counters - sub-launches of the marker screen by path (screen.hip): workgroup per pair / sliced queries / inverted index with the
+// count row in LDS, by waves / the same by lanes / inverted index with the count matrix in HBM / the single query's screen_kernel
+enum { SCREEN_BRUTE = 0, SCREEN_SLICED, SCREEN_INV_WAVE, SCREEN_INV_LANE, SCREEN_INV_GLOBAL, SCREEN_SINGLE, SCREEN_COUNT };
 struct psk_ctx {
     int device = 0;
     bool timing = false;
@@ -116,6 +119,8 @@ struct psk_ctx {
     // launches of the selection's and the reduce's size tiers, and the pairs a completed batch's status words name for the selection's lists (psk_ctx_tier_stats;
     // counted where the host decides or reads the status it copies back anyway, read by tests - no decision reads them)
     std::atomic<uint64_t> tier[TIER_COUNT] = {};
+    // sub-launches of the marker screen by path (psk_ctx_screen_stats; counted beside the launches, read by tests - no decision reads them)
+    std::atomic<uint64_t> screen_path[SCREEN_COUNT] = {};
     // the cluster stage's last call (cluster.hip; psk_ctx_cluster_stats): undirected edges, greedy rounds that decided a vertex, hook passes of single linkage
     std::atomic<uint64_t> cl_edges{0}, cl_rounds{0}, cl_hooks{0};
     // the linkage forest's last call that reached the device (cluster.hip; psk_ctx_forest_stats): undirected edges, rounds that hooked a component, pointer-jump launches
@@ -679,6 +684,8 @@ psk_status ensure_probe(Lane* ctx, const psk_sketch* const* refs, uint32_t n);
 __device__ __forceinline__ uint32_t probe_line(uint32_t km, uint32_t lines) { return __umulhi(km * 2654435761u, lines); }
 psk_status screen_impl(Lane* ctx, psk_db* db, const psk_sketch* query, double screen_val, int rescue_small,
                        uint8_t* pass, uint32_t* shared);
+// the screen step of query_many_impl alone: pass[n_queries][n_refs] on the host, insertion order (psk_screen_many)
+psk_status screen_many_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, double screen_val, int rescue_small, uint8_t* pass);
 // ci (null: no intervals): the bootstrap bounds of every pair into ci_lo[] / ci_hi[]
 psk_status chain_pairs_impl(Lane* ctx, const psk_sketch* const* refs, const psk_sketch* const* queries, uint32_t n,
                             const psk_query_opts* o, psk_hit* out, const psk_ci_opts* ci = nullptr, float* ci_lo = nullptr, float* ci_hi = nullptr);

@@ -51,6 +51,7 @@ psk_status screen_impl(Lane* ctx, psk_db* db, const psk_sketch* q, double screen
     const uint64_t* qm = q->store ? q->store->markers + q->marker_off : nullptr;
     double thresh = pow(screen_val, (double)K_MARKER);
     ctx->t_begin(K_SCREEN);
+    ctx->dev->screen_path[SCREEN_SINGLE]++;
     hipLaunchKernelGGL(screen_kernel, dim3(n), dim3(256), 0, st, (const MarkerSet*)db->d_marker_ptr.p, qm, (uint32_t)q->n_markers,
                        thresh, rescue_small, d_pass, d_shared);
     ctx->t_end();
@@ -332,6 +333,7 @@ psk_status screen_many_device(Lane* ctx, psk_db* db, const psk_sketch* const* qu
                 lds_attr = true;
             }
             const bool wave_off = sw.screen_wave.off();      // "0": one lane per marker, binary search over the whole index (A/B, tests)
+            ctx->dev->screen_path[!wave_off && db->inv_n ? SCREEN_INV_WAVE : SCREEN_INV_LANE]++;
             if (!wave_off && db->inv_n)
                 hipLaunchKernelGGL(inv_screen_wave_kernel, dim3(m), dim3(512), 4 * (size_t)n, st, (const MarkerSet*)db->d_marker_ptr.p, d_q,
                                    (const uint64_t*)db->inv_key.p, (const uint32_t*)db->inv_ref.p, (const uint32_t*)db->inv_bucket.p, 2 * K_MARKER - db->inv_bits, n, thresh, rescue_small, pass_b);
@@ -339,6 +341,7 @@ psk_status screen_many_device(Lane* ctx, psk_db* db, const psk_sketch* const* qu
             hipLaunchKernelGGL(inv_screen_lds_kernel, dim3(m), dim3(512), 4 * (size_t)n, st, (const MarkerSet*)db->d_marker_ptr.p, d_q,
                                (const uint64_t*)db->inv_key.p, (const uint32_t*)db->inv_ref.p, (uint32_t)db->inv_n, n, thresh, rescue_small, pass_b);
         } else if (use_inv) {
+            ctx->dev->screen_path[SCREEN_INV_GLOBAL]++;
             PSK_HIP(hipMemcpyAsync(d_qoff, qoff.data(), 4 * (size_t)(m + 1), hipMemcpyHostToDevice, st));
             PSK_HIP(hipMemsetAsync(d_cnt, 0, 4 * (size_t)m * n, st));
             if (items && db->inv_n)
@@ -347,14 +350,52 @@ psk_status screen_many_device(Lane* ctx, psk_db* db, const psk_sketch* const* qu
             const size_t cells = (size_t)m * n;
             hipLaunchKernelGGL(inv_decide_kernel, dim3((uint32_t)((cells + 255) / 256)), dim3(256), 0, st, (const MarkerSet*)db->d_marker_ptr.p, d_q, n, m, d_cnt, thresh, rescue_small, pass_b);
         } else if (max_qm > 4 * SCREEN_SLICE && (uint64_t)m * n <= (1u << 22)) {   // few pairs of very large marker sets: slice the queries
+            ctx->dev->screen_path[SCREEN_SLICED]++;
             PSK_HIP(hipMemsetAsync(d_cnt, 0, 4 * (size_t)m * n, st));
             hipLaunchKernelGGL(screen_slice_kernel, dim3(n, m, (max_qm + SCREEN_SLICE - 1) / SCREEN_SLICE), dim3(256), 0, st, (const MarkerSet*)db->d_marker_ptr.p, d_q, n, d_cnt);
             const size_t cells = (size_t)m * n;
             hipLaunchKernelGGL(inv_decide_kernel, dim3((uint32_t)((cells + 255) / 256)), dim3(256), 0, st, (const MarkerSet*)db->d_marker_ptr.p, d_q, n, m, d_cnt, thresh, rescue_small, pass_b);
         } else {
+            ctx->dev->screen_path[SCREEN_BRUTE]++;
             hipLaunchKernelGGL(screen_many_kernel, dim3(n, m), dim3(256), 0, st, (const MarkerSet*)db->d_marker_ptr.p, d_q, n, thresh, rescue_small, pass_b);
         }
         ctx->t_end();
     }
+    return PSK_OK;
+}
+
+// psk_screen_many: the screen step of query_many_impl and nothing behind it - the same handling of stale tables under the exclusive lock, one read of the switches,
+// screen_many_device into lane scratch, one synchronisation, the matrix copied out
+psk_status screen_many_impl(Lane* ctx, psk_db* db, const psk_sketch* const* queries, uint32_t n_queries, double screen_val, int rescue_small, uint8_t* pass) {
+    hipStream_t st = ctx->stream;
+    const Switches sw = Switches::read();
+    for (uint32_t i = 0; i < n_queries; i++) if (!queries[i]) { psk_set_error("screen_many: NULL query %u", i); return PSK_EINVAL; }
+    std::shared_lock<std::shared_mutex> sh(db->rw);
+    const uint32_t n = (uint32_t)db->refs.size();
+    if (n == 0 || n_queries == 0) return PSK_OK;
+    if ((uint64_t)n * n_queries > (1ull << 30)) { psk_set_error("screen_many: %u queries x %u references exceed 2^30 cells", n_queries, n); return PSK_ELIMIT; }
+    const char* force = sw.screen.get();
+    const bool want_inv = force ? !strcmp(force, "inv") : ((uint64_t)n * n_queries >= (1ull << 18));
+    if (db->tables_dirty || (want_inv && db->inv_dirty)) {
+        sh.unlock();
+        psk_status rc = PSK_OK;
+        {
+            std::unique_lock<std::shared_mutex> ex(db->rw);
+            if (db->refs.size() != n) rc = PSK_EINVAL;
+            if (rc == PSK_OK) rc = upload_marker_table(ctx, db);
+            if (rc == PSK_OK && want_inv) rc = build_inverted(ctx, db);
+            if (rc == PSK_OK && hipStreamSynchronize(st) != hipSuccess) rc = PSK_EHIP;
+        }
+        sh.lock();
+        if (db->refs.size() != n) { psk_set_error("the database was modified while it was being screened"); return PSK_EINVAL; }
+        PSK_TRY(rc);
+    }
+    const size_t cells = (size_t)n_queries * n;
+    PSK_TRY(ctx->q_i.reserve(cells + 256));
+    uint8_t* d_pass = (uint8_t*)ctx->q_i.p;
+    ScreenStaging keep;
+    PSK_TRY(screen_many_device(ctx, db, queries, n_queries, screen_val, rescue_small, d_pass, keep, sw));
+    PSK_HIP(hipMemcpyAsync(pass, d_pass, cells, hipMemcpyDeviceToHost, st));
+    PSK_HIP(hipStreamSynchronize(st));
     return PSK_OK;
 }

@@ -955,6 +955,24 @@ class Database:
         with Database._Borrow(self, False):
             return self._query(name, contigs, seed, learned_ani, median, robust, cutoff, faster_small)
 
+    SCREEN_PATHS = ("brute", "sliced", "inv_wave", "inv_lane", "inv_global", "single")      # psk_ctx_screen_stats, in its order
+
+    def screen_many(self, sketches, cutoff=None, faster_small=False):
+        """The marker screen of `query_sketches` alone (psk_screen_many): a bool array [len(sketches)][len(self)], True where the pair would be chained - by
+        the path and the sub-launches the query would take. Nothing behind the screen runs, so markers-only sketches are fine."""
+        n, n_refs = len(sketches), self._lib.psk_db_size(self._h)
+        flags = np.zeros((n, n_refs), np.uint8)
+        arr = (C.c_void_p * max(n, 1))(*[s._h for s in sketches])
+        with Database._Borrow(self, False):
+            _capi.check(self._lib.psk_screen_many(self._h, arr, n, float(cutoff) if cutoff else 0.80, int(not faster_small), flags.ctypes.data_as(C.c_void_p)))
+        return flags.view(np.bool_)
+
+    def screen_stats(self, reset=False):
+        """Sub-launches of the marker screen on this database's context since the last reset, by path (psk_ctx_screen_stats): a dict over `SCREEN_PATHS`."""
+        out = (C.c_uint64 * len(self.SCREEN_PATHS))()
+        _capi.check(self._lib.psk_ctx_screen_stats(self._ctx._h, out, len(self.SCREEN_PATHS), int(bool(reset))))
+        return dict(zip(self.SCREEN_PATHS, (int(x) for x in out)))
+
     def locality(self):
         """The database's internal order of its references, in which relatives are neighbours (the seed indexes are laid out by it; names, indices and
         hits stay in insertion order). Returns `(slot_of, n_groups)`: a numpy uint32 array with the position of every reference, and the number of

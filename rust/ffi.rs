@@ -159,6 +159,10 @@ extern "C" {
     // the two halves of `query`, for a disk-backed Database (markers resident, sketches loaded per query)
     pub fn psk_screen(db: *mut PskDb, q: *const PskSketch, screen_val: f64, rescue_small: c_int,
                       pass: *mut u8, shared: *mut u32) -> c_int;
+    // the screen step of psk_query_many alone: pass[n * psk_db_size] on the host, insertion order; and the screen's sub-launches by path (six counters). Both
+    // added after PSK_ABI_VERSION 7 without raising it
+    pub fn psk_screen_many(db: *mut PskDb, qs: *const *const PskSketch, n: u32, screen_val: f64, rescue_small: c_int, pass: *mut u8) -> c_int;
+    pub fn psk_ctx_screen_stats(ctx: *mut PskCtx, out: *mut u64, n: c_int, reset: c_int) -> c_int;
     pub fn psk_chain(ctx: *mut PskCtx, refs: *const *const PskSketch, n: u32, q: *const PskSketch,
                      o: *const PskQueryOpts, out: *mut PskHit) -> c_int;
     // confidence intervals of the ANI (skani's --ci): the 5 % - 95 % bootstrap interval of every pair. Added after PSK_ABI_VERSION 7 without raising it: look the
